@@ -1,6 +1,6 @@
 """bench.py — agent·steps/sec of the cm-flock-v0 step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 One "step" = one env.step of every env on this rank: one HIP launch of
@@ -12,9 +12,12 @@ Weak scaling: every rank runs its own E envs (global env ids rank*E .. rank*E+E-
 no collective on the data path; one all-reduce of counters after the timed region.
 
 Rank 0 prints ONE JSON line. `roofline` prices the step kernel against HBM with the
-algorithmic bytes of SURVEY.md §8(d) (B_alg = 107 B per agent-step); `cpu_baseline`
-times the CPU oracle (oracle/, a C restatement of the reference's path) on this
-host's cores over a bounded sample of the same workload.
+algorithmic bytes of SURVEY.md §8(d) (B_alg = 107 B per agent-step). A plain run times
+the K steps and nothing else. `--full` adds the runs of their own: `per_step_launch`
+(the same window again, one launch per step) and `cpu_baseline`, which times the CPU
+oracle (oracle/, a C restatement of the reference's path) on this host's cores over a
+bounded sample of the same workload, with the chain floor from its level structure.
+`--dump-outputs DIR` writes the last timed step's outputs as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -196,6 +199,28 @@ def lib_sha256():
         return hashlib.sha256(f.read()).hexdigest()
 
 
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # --dump-outputs: all files of one rank together stay below 64 MB
+
+
+def dump_outputs(dirname, arrays, n_envs, seed, suffix=""):
+    """--dump-outputs: write the last timed step's outputs ({name: tensor [E, ...]}) as
+    DIR/<name><suffix>.npy, float64 where the output is float64 and float32 otherwise (the integer
+    outputs are small enough to be exact). When all envs would exceed DUMP_BUDGET_BYTES, every array
+    keeps the same seeded sample of envs, ascending, listed in DIR/env_index<suffix>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    width = {k: 8 if v.dtype == torch.float64 else 4 for k, v in arrays.items()}
+    per_env = sum(width[k] * (v.numel() // max(1, n_envs)) for k, v in arrays.items()) + 8
+    keep = min(n_envs, max(1, DUMP_BUDGET_BYTES // per_env))
+    idx = np.arange(n_envs)
+    if keep < n_envs:
+        idx = np.sort(np.random.default_rng(seed).choice(n_envs, size=keep, replace=False))
+    for k, v in arrays.items():
+        a = v[torch.from_numpy(idx).to(v.device)].cpu().numpy()
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), a.astype(np.float64 if width[k] == 8 else np.float32))
+    np.save(os.path.join(dirname, f"env_index{suffix}.npy"), idx.astype(np.float64))
+    return keep
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -251,7 +276,17 @@ def main():
     ap.add_argument("--agents", type=int, default=64)
     ap.add_argument("--flocks", type=int, default=1, help="targets = i // (agents / flocks) (config 3: 4)")
     ap.add_argument("--seed", type=int, default=0x6D61636D)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline window: the same window again with one launch per step "
+                         "(per_step_launch), and the CPU oracle baseline with the Gauss-Seidel chain floor "
+                         "(cpu_baseline, roofline.chain_*). Off by default: a plain run sets up, warms up, "
+                         "times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the outputs of the last timed step (what the caller of "
+                         "the timed launch receives for it) as DIR/<name>.npy, float32 or float64; a seeded "
+                         "sample of envs (DIR/env_index.npy) when all of them would pass 64 MB. N ranks: "
+                         "<name>.rank<r>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--env", choices=("flock", "tdm"), default="flock",
                     help="flock: cm-flock-v0 (the metric); tdm: cm-tdm-v0 (config 4, --teams)")
@@ -268,8 +303,8 @@ def main():
                     help="rollout: the K timed steps in one launch, each env's wave running its steps back to "
                          "back (random: macm_world_rollout over the actions drawn in advance; bots: "
                          "macm_world_rollout_bots, the bot acting inside the launch; N <= 64, the workgroup path "
-                         "launches per step either way); step: one launch per step (plus the bot's). A rollout run "
-                         "also times the per-step launches on the same window (per_step_launch)")
+                         "launches per step either way); step: one launch per step (plus the bot's). With --full a "
+                         "rollout run also times the per-step launches on the same window (per_step_launch)")
     ap.add_argument("--traffic-json", default=None)
     ap.add_argument("--total-envs", type=int, default=0,
                     help="strong scaling: split this many envs over the ranks (contiguous global env ids, "
@@ -477,6 +512,13 @@ def main():
         st = world_h.get_state()
         np.savez(f"{args.dump_final}.rank{rank}.npz", env_offset=e_off, counters=world_h.counters(),
                  **{k: v for k, v in st.items() if isinstance(v, np.ndarray)})
+    if args.dump_outputs:
+        # the last timed step's outputs: its row of the trajectory buffers, else the world's output set
+        names = ("obs", "nbr_id", "reward", "collided", "done") if args.env == "flock" else world_h._TRAJ_KEYS
+        last = ({k: traj[k][K - 1] for k in names} if traj is not None
+                else {k: getattr(world_h, k) for k in names})
+        kept = dump_outputs(args.dump_outputs, last, E, args.seed, "" if world == 1 else f".rank{rank}")
+        log(f"rank {rank}: last step's outputs of {kept} of {E} envs written to {args.dump_outputs}")
 
     if rank == 0:
         # float64 obs: the 4 obs values take 8 B each (Flock +16 B; TDM +16 B per observed agent)
@@ -626,7 +668,7 @@ def main():
         else:
             out["counters"] = {"alive_agent_steps": int(cnt[0]), "melee_attacks": int(cnt[1]),
                                "deaths": int(cnt[2]), "done_env_steps": int(cnt[3])}
-        if rollout and world == 1:
+        if args.full and rollout and world == 1:
             # the same window again with one launch per step (what a closed-loop policy needs)
             if args.env == "flock":
                 vec.reset()
@@ -637,7 +679,7 @@ def main():
             el2, ev2, _ = timed_window(False)
             out["per_step_launch"] = {"value": E * N * K / el2, "ms_per_step": el2 / K * 1e3,
                                       "kernel_ms_per_step": ev2 / K}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("timing CPU baseline (oracle) ...")
             if args.env == "flock":
                 # the GPU leg's own actions when the window is short (the driver's 25 steps)

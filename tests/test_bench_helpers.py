@@ -55,6 +55,29 @@ def test_tdm_algorithmic_bytes(bench):
     assert bench.b_alg_tdm(32, obs_f64=True) == 670 + 31 * 16
 
 
+def test_dump_outputs_writes_float_arrays_and_a_seeded_env_sample(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float64 outputs stay float64, everything else is written as float32 (exact for
+    the small integers); past the byte budget every array keeps the same seeded, ascending env sample."""
+    import torch
+    E = 50
+    g = torch.Generator().manual_seed(1)
+    arrs = dict(obs=torch.randn(E, 8, 7, 4, generator=g), health=torch.randn(E, 8, dtype=torch.float64, generator=g),
+                mask=torch.randint(0, 2, (E, 8, 7), dtype=torch.uint8, generator=g),
+                winner=torch.full((E,), -1, dtype=torch.int32))
+    assert bench.dump_outputs(str(tmp_path / "all"), arrs, E, 3) == E
+    for k, v in arrs.items():
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype == (np.float64 if k == "health" else np.float32)
+        np.testing.assert_array_equal(a, v.numpy().astype(a.dtype))
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 20000)
+    kept = [bench.dump_outputs(str(tmp_path / d), arrs, E, 3, ".rank1") for d in ("s1", "s2")]
+    idx = np.load(tmp_path / "s1" / "env_index.rank1.npy").astype(np.int64)
+    assert kept[0] == kept[1] == len(idx) < E and (np.diff(idx) > 0).all()
+    np.testing.assert_array_equal(idx, np.load(tmp_path / "s2" / "env_index.rank1.npy").astype(np.int64))
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "obs.rank1.npy"), arrs["obs"].numpy()[idx])
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= 20000 + 5 * 128
+
+
 def test_pmc_summary_matches_the_rollout_kernel(tmp_path):
     pmc = load("pmc_summary_mod", "tools/pmc_summary.py")
     p = tmp_path / "run_counter_collection.csv"

@@ -3,7 +3,8 @@ both on the box's one GPU, gloo for the counter all-reduce since RCCL needs one 
 Each rank steps its own shard of global env ids; the reduced counters must cover both shards
 and the line must report the whole job. The RCCL flavour (`--dist-backend nccl`, the default) needs one GPU
 per rank, so on this box it runs as one rank under torchrun (test_rccl_single_rank_under_torchrun);
-its multi-rank form runs in the driver's 8-GPU scaling bench."""
+its multi-rank form runs in the driver's 8-GPU scaling bench.
+Also the single-process command line: a plain run (headline only, `--dump-outputs`) and `--full`."""
 import json
 import os
 import socket
@@ -105,6 +106,50 @@ def test_strong_split_two_ranks_equal_single_process(tmp_path, extra):
             np.testing.assert_array_equal(pad(part[k]), pad(ref[k][o:o + n]), err_msg=f"rank {r} {k}")
         seen += n
     assert seen == T
+
+
+def test_plain_run_times_only_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` carries the headline fields and none of the
+    `--full` measurements; `--dump-outputs DIR` writes the last timed step's outputs, equal to the last
+    trajectory row of the same launches made here (same seed, same actions)."""
+    import numpy as np
+    import torch
+    from gym_macm.vec import FlockVec
+    K, W, E, N, seed = 4, 2, 96, 64, 0x6D61636D
+    d = _run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+              "--envs", str(E), "--dump-outputs", str(tmp_path / "out")])
+    assert d["steps"] == K and d["warmup"] == W and d["unit"] == "agent·steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(E * N / (d["ms_per_step"] * 1e-3))
+    assert d["cpu_baseline"] is None and "per_step_launch" not in d and "chain_frac" not in d["roofline"]
+    vec = FlockVec(E, n_agents=[N], seed=seed, device="cuda:0")
+    gen = torch.Generator(device="cuda:0")
+    gen.manual_seed(seed + 1)
+    acts = torch.randint(0, 3, (W + K, E, N, 3), dtype=torch.uint8, device="cuda:0", generator=gen)
+    sh = torch.cuda.current_stream().cuda_stream
+    traj = vec.world.trajectory_buffers(K)
+    vec.world.rollout_raw(acts.data_ptr(), W, sh)
+    vec.world.rollout_traj_raw(acts[W:].data_ptr(), K, traj, sh)
+    torch.cuda.synchronize()
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(f"{k}.npy" for k in list(traj) + ["env_index"])
+    np.testing.assert_array_equal(np.load(tmp_path / "out" / "env_index.npy"), np.arange(E))
+    for k, v in traj.items():
+        a = np.load(tmp_path / "out" / f"{k}.npy")
+        assert a.dtype == np.float32
+        np.testing.assert_array_equal(a, v[K - 1].cpu().numpy().astype(np.float32), err_msg=k)
+
+
+def test_full_run_adds_the_per_step_launches_and_the_cpu_baseline():
+    """`--full`: the same window again with one launch per step, the CPU oracle baseline on the GPU
+    leg's own actions and the chain floor from its levels, beside an unchanged headline."""
+    K, W, E = 4, 2, 96
+    d = _run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+              "--envs", str(E), "--full", "--cpu-budget", "2"])
+    assert d["steps"] == K and d["ms_per_step"] > 0 and d["counters"]["agent_steps"] == E * 64 * K
+    assert d["per_step_launch"]["ms_per_step"] > 0 and d["per_step_launch"]["value"] > 0
+    assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0
+    assert "the GPU leg's own actions" in d["cpu_baseline"]["sample"]
+    assert 0 < d["roofline"]["chain_frac"] and d["roofline"]["chain_floor"]["steps_sampled"] == K
 
 
 @pytest.mark.parametrize("extra", [[], ["--agents", "100"]])

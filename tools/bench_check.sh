@@ -4,7 +4,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/${1:-bc}
 mkdir -p "$OUT"
-run() { local name=$1; shift; timeout -k 10 300 python bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; local rc=$?; echo "$name rc=$rc"; return $rc; }
+run() { local name=$1; shift; timeout -k 10 300 python bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; local rc=$?; echo "$name rc=$rc"; return $rc; }
 run m_w5 --steps 20 --warmup 5 && \
 run m_w5_f64 --steps 20 --warmup 5 --obs-f64 && \
 run m_1000 --steps 1000 --warmup 100 && \

@@ -5,7 +5,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/${1:-cfg}
 mkdir -p "$OUT"
-run() { local name=$1; shift; timeout -k 10 400 python bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; local rc=$?; echo "$name rc=$rc"; return $rc; }
+run() { local name=$1; shift; timeout -k 10 400 python bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; local rc=$?; echo "$name rc=$rc"; return $rc; }
 run m_4096x64 --steps 1000 --warmup 100 && \
 run c2_1024x64 --envs 1024 --agents 64 --steps 300 --warmup 30 && \
 run c3_4096x256_4flocks --envs 4096 --agents 256 --flocks 4 --steps 60 --warmup 5 && \

@@ -12,7 +12,7 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 st() { echo "$1 rc=$2" | tee -a "$OUT/status.txt"; [ "$2" -eq 0 ] || exit "$2"; }
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q -rf --timeout 300 --timeout-method thread -p no:cacheprovider > "$OUT/pytest.log" 2>&1; st pytest $?
 timeout -k 10 180 python __graft_entry__.py smoke > "$OUT/smoke.log" 2>&1; st smoke $?
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/m_driver.json" 2> "$OUT/m_driver.err"; st m_driver $?
+timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/m_driver.json" 2> "$OUT/m_driver.err"; st m_driver $?
 for x in "$@"; do
   case $x in
     overwrite) timeout -k 10 300 python bench.py --steps 20 --warmup 5 --outputs overwrite --no-cpu-baseline > "$OUT/m_overwrite.json" 2> "$OUT/m_overwrite.err"; st overwrite $? ;;

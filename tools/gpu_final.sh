@@ -33,9 +33,9 @@ stop $? pmc_summary_flock
 python tools/pmc_summary.py "$OUT/pmc_tdm" --kernel "env_step_w64<1, 32, float, false>" --envs 4096 --agents 32 \
     -o "$OUT/pmc_tdm_step.json" >> "$OUT/pmc_summary.log" 2>&1
 stop $? pmc_summary_tdm
-timeout -k 10 300 python bench.py --traffic-json "$OUT/pmc_flock_step.json" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python bench.py --full --traffic-json "$OUT/pmc_flock_step.json" > "$OUT/bench.json" 2> "$OUT/bench.err"
 stop $? bench
-timeout -k 10 300 python bench.py --env tdm --traffic-json "$OUT/pmc_tdm_step.json" > "$OUT/bench_tdm.json" 2> "$OUT/bench_tdm.err"
+timeout -k 10 300 python bench.py --full --env tdm --traffic-json "$OUT/pmc_tdm_step.json" > "$OUT/bench_tdm.json" 2> "$OUT/bench_tdm.err"
 stop $? bench_tdm
 bash tools/configs.sh "$NAME/configs" > "$OUT/configs.log" 2>&1
 stop $? configs

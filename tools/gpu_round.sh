@@ -16,14 +16,14 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q -rf --timeout 120 --timeou
 stop_if_crash $? pytest_gpu
 timeout -k 10 180 python __graft_entry__.py smoke > "$OUT/smoke.log" 2>&1
 stop_if_crash $? smoke
-timeout -k 10 300 python bench.py --steps 300 --warmup 30 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python bench.py --steps 300 --warmup 30 --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 stop_if_crash $? bench
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/$OUT/prof" -o run -- \
   python3 "$GRAFT_REPO_ROOT/bench.py" --steps 200 --warmup 20 --no-cpu-baseline > "$GRAFT_REPO_ROOT/$OUT/prof_bench.json" 2> "$GRAFT_REPO_ROOT/$OUT/prof.err"
 stop_if_crash $? rocprof
 cd "$GRAFT_REPO_ROOT"
-timeout -k 10 300 python bench.py --env tdm --steps 300 --warmup 30 > "$OUT/bench_tdm.json" 2> "$OUT/bench_tdm.err"
+timeout -k 10 300 python bench.py --env tdm --steps 300 --warmup 30 --full > "$OUT/bench_tdm.json" 2> "$OUT/bench_tdm.err"
 stop_if_crash $? bench_tdm
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/$OUT/prof_tdm" -o run -- \
