@@ -33,8 +33,16 @@
 // front; list entries and their impulses arrive in one round trip and stay in registers;
 // the chain runs at raised issue priority (s_setprio), the DFS walks scalar bit masks
 // through v_readlane / v_writelane, small islands keep their records in registers, and
-// bodies sit in LDS as float2; the all-pairs sweep reads records by LDS broadcast in two
+// bodies sit in LDS as float2; the nearest-neighbour sweep reads positions by LDS broadcast in two
 // interleaved chains; per-env counters instead of global atomics.
+//
+// New pairs come from the moved proxies only, as in b2BroadPhase::UpdatePairs: the incoming list
+// holds every overlap of the old fat AABBs (the init kernels build it with a full sweep, and each
+// step keeps it so), hence a pair of two proxies whose fat AABBs were not rewritten this step is
+// in the list exactly if it overlaps now, and only the columns of the rewritten ones are tested
+// (moved_pairs; ~4.5 of 64 per step at the metric config). A state injected with a list that lacks
+// an overlapping pair of resting bodies gets that contact when one of the two next moves, as in
+// Box2D.
 //
 // Exactness notes (checked by tests/test_gpu_parity.py against the oracle):
 //   * fixedRotation bodies have invI = 0 and w = 0, so every angular term in the
@@ -50,7 +58,7 @@ namespace macm {
 
 constexpr int W = 64;       // wavefront = one env's agent lanes
 // touching contacts per env held in LDS (indices fit uint8); more take the spill step. With s_adj
-// aliased onto s_tm and the sweep records over s_tn + s_tab the Flock kernel needs 8.3 KB of LDS:
+// aliased onto s_tm and the new fat AABBs and final positions over s_tn the Flock kernel needs 8.3 KB of LDS:
 // 19 waves per CU, so a 4096-env launch (16 per CU) has slack (at 16 per CU, -4% per step at M
 // and -7% in the bots closed loop; TCAP 224 fits 20 per CU but sends dense bots envs to the
 // spill step: profiles/r02/wave_levels)
@@ -166,13 +174,6 @@ __device__ __forceinline__ fvec2 mk2(float a, float b) {
   v.y = b;
   return v;
 }
-
-// One agent's record for the all-pairs sweep: read by LDS broadcast (2 x ds_read_b128).
-struct __align__(32) PairRec {
-  float4 fn;  // fat AABB after SynchronizeFixtures
-  float2 c;   // final position
-  float2 pad;
-};
 
 // v_readlane with a wave-uniform lane index: broadcast without an LDS round trip.
 __device__ __forceinline__ float bcast(float v, int j) {
@@ -597,74 +598,49 @@ struct WideLevels {
   }
 };
 
-struct SweepState {
-  uint32_t ov_lo, ov_hi;  // partner row of this lane's agent (written by lane j = row owner)
-  float best;             // nearest other agent: squared distance
-  int bj;                 //                      and index
+// ---- nearest neighbour: the all-pairs sweep (Flock) ---------------------------------------------
+// Unrolled at compile time over J < NCAP final positions, read from LDS by broadcast two per
+// ds_read_b128 (lanes >= N hold positions infinitely far away). The fat-AABB overlap test is not
+// part of this sweep: only the pairs of a proxy whose fat AABB was rewritten this step are tested
+// (moved_pairs below).
+struct NearState {
+  float best;  // nearest other agent: squared distance
+  int bj;      //                      and index
 };
 
-// One record of the all-pairs sweep, unrolled at compile time over J < NCAP (lanes
-// >= N hold dummies that overlap nothing and are infinitely far). Each lane shifts its
-// overlap bit for agent J into its own partner row (add-with-carry, below); the AABB /
-// distance differences run as packed float2 ops, each lane of which is the same IEEE
-// operation as the scalar form.
-// Records in flight during the sweep: record J + AH is requested while record J is tested,
-// so an LDS broadcast has AH records' worth of VALU work to arrive in (a single record's ~12
-// VALU do not cover the LDS latency with the other waves of the CU reading too).
-constexpr int kSweepAhead = 2;
+// position pairs in flight during the sweep: pair K + kNearAhead is requested while pair K is
+// used, so a broadcast has that many records' VALU work to arrive in
+constexpr int kNearAhead = 2;
 
-struct SweepRec {
-  float4 fn;
-  float2 c;
-};
-
-__device__ __forceinline__ SweepRec load_rec(const PairRec* s_pj, int j) {
-  SweepRec r;
-  r.fn = s_pj[j].fn;  // ds_read_b128
-  r.c = s_pj[j].c;    // ds_read_b64 (the pad is never read)
-  return r;
+// one compare -> mask -> select step of a running minimum on VCC: strict '<', so the lowest index
+// wins ties (mvmnt.py:194); lane J (self) is cleared from the compare mask on the scalar unit. The
+// asm also materialises the running minimum here (otherwise the compiler sinks the distance work
+// past the sweep and spills every record's position).
+template <int J>
+__device__ __forceinline__ void near_min(float d2, NearState& st) {
+  asm volatile(
+      "v_cmp_lt_f32 vcc, %2, %0\n\t"
+      "s_bitset0_b64 vcc, %3\n\t"
+      "v_cndmask_b32 %0, %0, %2, vcc\n\t"
+      "v_cndmask_b32_e64 %1, %1, %3, vcc"
+      : "+v"(st.best), "+v"(st.bj)
+      : "v"(d2), "i"(J)
+      : "vcc");
 }
 
-template <int J, int NCAP, bool NN>
-__device__ __forceinline__ void sweep_step(const PairRec* s_pj, SweepRec* win, fvec2 fn_lo, fvec2 fn_hi,
-                                           fvec2 cme, unsigned long long valid, int lane, SweepState& st) {
-  const SweepRec q = win[J % kSweepAhead];
-  if constexpr (J + kSweepAhead < NCAP) win[J % kSweepAhead] = load_rec(s_pj, J + kSweepAhead);
-  // b2TestOverlap(fn, fj) separates iff one of (fj.lo - fn.hi, fn.lo - fj.hi) > 0;
-  // for finite AABBs (and the +-inf dummies) that is max(...) > 0
-  const fvec2 a = mk2(q.fn.x, q.fn.y) - fn_hi;
-  const fvec2 b = fn_lo - mk2(q.fn.z, q.fn.w);
-  const float sepv = fmaxf(fmaxf(a.x, a.y), fmaxf(b.x, b.y));
-  // this lane's overlap bit for agent J (= bit J of its own partner row: the test is
-  // symmetric, both orders compare the same four differences) shifted into a per-lane
-  // register by add-with-carry (acc = 2 acc + bit): bit J lands at 31 - (J & 31) and is
-  // bit-reversed after the sweep; the valid mask is applied there
-  (void)valid;
-  if constexpr (J < 32)
-    asm volatile("v_cmp_nlt_f32 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(st.ov_lo) : "v"(sepv) : "vcc");
-  else
-    asm volatile("v_cmp_nlt_f32 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(st.ov_hi) : "v"(sepv) : "vcc");
-  if constexpr (NN) {
-    const fvec2 d = mk2(q.c.x, q.c.y) - cme;  // other.position - agent.position
-    const fvec2 dd = d * d;
-    const float d2 = dd.x + dd.y;             // b2DistanceSquared(other, agent)
-    // strict '<': lowest index wins ties (mvmnt.py:194); lane J (self) is cleared
-    // from the compare mask on the scalar unit. The asm also materialises the
-    // running minimum here (otherwise the compiler sinks the distance work past the
-    // sweep and spills every record's position).
-    asm volatile(
-        "v_cmp_lt_f32 vcc, %2, %0\n\t"
-        "s_bitset0_b64 vcc, %3\n\t"
-        "v_cndmask_b32 %0, %0, %2, vcc\n\t"
-        "v_cndmask_b32_e64 %1, %1, %3, vcc"
-        : "+v"(st.best), "+v"(st.bj)
-        : "v"(d2), "i"(J)
-        : "vcc");
-    (void)lane;
-  }
+// Records 2K and 2K + 1 of a single chain (NCAP = 32); the differences as packed float2 ops, each
+// lane of which is the same IEEE operation as the scalar form.
+template <int K, int NCAP>
+__device__ __forceinline__ void near_step(const float4* s_pc2, float4* win, fvec2 cme, NearState& st) {
+  const float4 q = win[K % kNearAhead];
+  if constexpr (K + kNearAhead < NCAP / 2) win[K % kNearAhead] = s_pc2[K + kNearAhead];
+  const fvec2 d0 = mk2(q.x, q.y) - cme, d1 = mk2(q.z, q.w) - cme;  // other.position - agent.position
+  const fvec2 dd0 = d0 * d0, dd1 = d1 * d1;
+  near_min<2 * K>(dd0.x + dd0.y, st);  // b2DistanceSquared(other, agent)
+  near_min<2 * K + 1>(dd1.x + dd1.y, st);
   // keep the scheduler from hoisting every record's LDS read (register pressure)
-  if constexpr ((J & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-  if constexpr (J + 1 < NCAP) sweep_step<J + 1, NCAP, NN>(s_pj, win, fn_lo, fn_hi, cme, valid, lane, st);
+  if constexpr ((K & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+  if constexpr (K + 1 < NCAP / 2) near_step<K + 1, NCAP>(s_pc2, win, cme, st);
 }
 
 // The sweep's differences as scalar VALU (SCAL) or as v_pk_* pairs: with 16 envs per CU (the
@@ -673,68 +649,80 @@ __device__ __forceinline__ void sweep_step(const PairRec* s_pj, SweepRec* win, f
 // with N > 32 picks by the number of envs.
 constexpr int kScalarSweepMinEnvs = 2048;
 
-// NCAP = 64 with the nearest neighbour: the records of the two halves are taken in turns
-// (0, 32, 1, 33, ...) with a running minimum per half, so the two loop-carried chains (the
-// overlap bits of ov_lo / ov_hi and the minimum of each half) are independent and their
-// compare -> mask -> select steps issue interleaved; each half's compare result goes to its own
-// SGPR pair instead of VCC. Each half still scans its records in increasing j with strict '<',
-// and the halves merge with the lower half winning ties, which is the single scan's result.
-struct SweepState2 {
-  uint32_t ov_lo, ov_hi;
+// NCAP = 64: the records of the two halves are taken in turns (0, 32, 1, 33, ...) with a running
+// minimum per half, so the two loop-carried chains are independent and their compare -> mask ->
+// select steps issue interleaved; each half's compare result goes to its own SGPR pair instead of
+// VCC. Each half still scans its records in increasing j with strict '<', and the halves merge with
+// the lower half winning ties, which is the single scan's result.
+struct NearState2 {
   float best_a, best_b;
   int bj_a, bj_b;
 };
 
-template <int S, int AH, bool SCAL>
-__device__ __forceinline__ void sweep2_step(const PairRec* s_pj, SweepRec* win, fvec2 fn_lo, fvec2 fn_hi,
-                                            fvec2 cme, SweepState2& st) {
-  constexpr int JA = S, JB = 32 + S;  // records of this step: JA (lower half), JB (upper half)
-  const SweepRec qa = win[(2 * S) % AH], qb = win[(2 * S + 1) % AH];
-  // the records of step S + AH / 2 (record order 0, 32, 1, 33, ...)
-  if constexpr (2 * S + AH < 64) {
-    constexpr int K = 2 * S + AH;
-    win[(2 * S) % AH] = load_rec(s_pj, (K & 1) ? 32 + (K >> 1) : (K >> 1));
-  }
-  if constexpr (2 * S + 1 + AH < 64) {
-    constexpr int K = 2 * S + 1 + AH;
-    win[(2 * S + 1) % AH] = load_rec(s_pj, (K & 1) ? 32 + (K >> 1) : (K >> 1));
-  }
-  float sa, sb, d2a, d2b;
+template <int JA, int JB, bool SCAL>
+__device__ __forceinline__ void near2_min(float ax, float ay, float bx, float by, fvec2 cme, NearState2& st) {
+  float d2a, d2b;
   if constexpr (SCAL) {  // see kScalarSweepMinEnvs
-  sa = fmaxf(fmaxf(qa.fn.x - fn_hi.x, qa.fn.y - fn_hi.y), fmaxf(fn_lo.x - qa.fn.z, fn_lo.y - qa.fn.w));
-  sb = fmaxf(fmaxf(qb.fn.x - fn_hi.x, qb.fn.y - fn_hi.y), fmaxf(fn_lo.x - qb.fn.z, fn_lo.y - qb.fn.w));
-  const float dax = qa.c.x - cme.x, day = qa.c.y - cme.y, dbx = qb.c.x - cme.x, dby = qb.c.y - cme.y;
-  d2a = dax * dax + day * day;
-  d2b = dbx * dbx + dby * dby;
+    const float dax = ax - cme.x, day = ay - cme.y, dbx = bx - cme.x, dby = by - cme.y;
+    d2a = dax * dax + day * day;
+    d2b = dbx * dbx + dby * dby;
   } else {
-  const fvec2 aa = mk2(qa.fn.x, qa.fn.y) - fn_hi, ba = fn_lo - mk2(qa.fn.z, qa.fn.w);
-  const fvec2 ab = mk2(qb.fn.x, qb.fn.y) - fn_hi, bb = fn_lo - mk2(qb.fn.z, qb.fn.w);
-  sa = fmaxf(fmaxf(aa.x, aa.y), fmaxf(ba.x, ba.y));
-  sb = fmaxf(fmaxf(ab.x, ab.y), fmaxf(bb.x, bb.y));
-  const fvec2 da = mk2(qa.c.x, qa.c.y) - cme, db = mk2(qb.c.x, qb.c.y) - cme;
-  const fvec2 dda = da * da, ddb = db * db;
-  d2a = dda.x + dda.y;
-  d2b = ddb.x + ddb.y;
+    const fvec2 da = mk2(ax, ay) - cme, db = mk2(bx, by) - cme;
+    const fvec2 dda = da * da, ddb = db * db;
+    d2a = dda.x + dda.y;
+    d2b = ddb.x + ddb.y;
   }
-  unsigned long long ca, cb, ma, mb;
+  unsigned long long ma, mb;
   asm volatile(
-      "v_cmp_nlt_f32_e64 %[ca], 0, %[sa]\n\t"
-      "v_cmp_nlt_f32_e64 %[cb], 0, %[sb]\n\t"
       "v_cmp_lt_f32_e64 %[ma], %[da], %[ba]\n\t"
       "v_cmp_lt_f32_e64 %[mb], %[db], %[bb]\n\t"
-      "v_addc_co_u32_e64 %[lo], %[ca], %[lo], %[lo], %[ca]\n\t"
-      "v_addc_co_u32_e64 %[hi], %[cb], %[hi], %[hi], %[cb]\n\t"
       "s_bitset0_b64 %[ma], %[JA]\n\t"
       "s_bitset0_b64 %[mb], %[JB]\n\t"
       "v_cndmask_b32_e64 %[ba], %[ba], %[da], %[ma]\n\t"
       "v_cndmask_b32_e64 %[ja], %[ja], %[JA], %[ma]\n\t"
       "v_cndmask_b32_e64 %[bb], %[bb], %[db], %[mb]\n\t"
       "v_cndmask_b32_e64 %[jb], %[jb], %[JB], %[mb]"
-      : [lo] "+v"(st.ov_lo), [hi] "+v"(st.ov_hi), [ba] "+v"(st.best_a), [bb] "+v"(st.best_b), [ja] "+v"(st.bj_a),
-        [jb] "+v"(st.bj_b), [ca] "=&s"(ca), [cb] "=&s"(cb), [ma] "=&s"(ma), [mb] "=&s"(mb)
-      : [sa] "v"(sa), [sb] "v"(sb), [da] "v"(d2a), [db] "v"(d2b), [JA] "i"(JA), [JB] "i"(JB));
-  if constexpr ((S & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-  if constexpr (S + 1 < 32) sweep2_step<S + 1, AH, SCAL>(s_pj, win, fn_lo, fn_hi, cme, st);
+      : [ba] "+v"(st.best_a), [bb] "+v"(st.best_b), [ja] "+v"(st.bj_a), [jb] "+v"(st.bj_b), [ma] "=&s"(ma),
+        [mb] "=&s"(mb)
+      : [da] "v"(d2a), [db] "v"(d2b), [JA] "i"(JA), [JB] "i"(JB));
+}
+
+// Step K: records 2K, 2K + 1 of the lower half (position pair K) and 32 + 2K, 33 + 2K of the upper
+// half (position pair 16 + K); win holds the pairs of kNearAhead steps, lower then upper.
+template <int K, bool SCAL>
+__device__ __forceinline__ void near2_step(const float4* s_pc2, float4* win, fvec2 cme, NearState2& st) {
+  const float4 qa = win[2 * (K % kNearAhead)], qb = win[2 * (K % kNearAhead) + 1];
+  if constexpr (K + kNearAhead < 16) {
+    win[2 * (K % kNearAhead)] = s_pc2[K + kNearAhead];
+    win[2 * (K % kNearAhead) + 1] = s_pc2[16 + K + kNearAhead];
+  }
+  near2_min<2 * K, 32 + 2 * K, SCAL>(qa.x, qa.y, qb.x, qb.y, cme, st);
+  near2_min<2 * K + 1, 33 + 2 * K, SCAL>(qa.z, qa.w, qb.z, qb.w, cme, st);
+  if constexpr ((K & 1) == 1) __builtin_amdgcn_sched_barrier(0);
+  if constexpr (K + 1 < 16) near2_step<K + 1, SCAL>(s_pc2, win, cme, st);
+}
+
+// ---- overlaps of the moved proxies ---------------------------------------------------------------
+// b2BroadPhase::UpdatePairs queries only the proxies that MoveProxy buffered, i.e. the bodies whose
+// fat AABB SynchronizeFixtures rewrote this step (movedm). For a pair with neither proxy moved the
+// overlap of the new fat AABBs is that of the old ones, which the incoming list already holds, and
+// the step uses its row only as row | oldm and row & ~oldm. So only the movedm columns are tested:
+// lane j's new fat AABB is broadcast by v_readlane and every lane evaluates the four differences
+// and the max of b2TestOverlap against its own (the same four differences in either order, so the
+// test is symmetric); each lane sets bit j of its row, and lane j takes the ballot as its whole row.
+// Returns this lane's row (before the valid / self masks).
+__device__ __forceinline__ unsigned long long moved_pairs(unsigned long long movedm, float4 fn, int lane) {
+  unsigned long long row = 0ull;
+  for (unsigned long long m = movedm; m; m &= m - 1ull) {  // wave-uniform, ascending j
+    const int j = __builtin_ctzll(m);
+    const float jx = bcast(fn.x, j), jy = bcast(fn.y, j), jz = bcast(fn.z, j), jw = bcast(fn.w, j);
+    // b2TestOverlap(fn, fj) separates iff one of (fj.lo - fn.hi, fn.lo - fj.hi) > 0
+    const float sepv = fmaxf(fmaxf(jx - fn.z, jy - fn.w), fmaxf(fn.x - jz, fn.y - jw));
+    const bool ov = !(0.0f < sepv);
+    const unsigned long long colj = __ballot(ov);
+    row |= (ov ? (1ull << j) : 0ull) | (lane == j ? colj : 0ull);
+  }
+  return row;
 }
 
 // New-pair compaction in descending (a, b) order: lane a owns the bitmask of
@@ -924,10 +912,11 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
   float* const s_tn = s_pool.tn;
   float* const s_tnx = s_tn;
   float* const s_tny = s_tn + TCAP;
-  PairRec* const s_pj = reinterpret_cast<PairRec*>(s_tn);
-  // s_pj spans s_tn and s_tab (adjacent in Pool): both are dead once the position solve ends
-  static_assert(offsetof(Pool, tab) == sizeof(float) * 2 * TCAP, "tab must follow tn");
-  static_assert(sizeof(PairRec) * W <= sizeof(float) * 2 * TCAP + sizeof(uint32_t) * TCAP, "s_pj must fit in s_tn + s_tab");
+  // after the position solve, over s_tn (dead once the velocity solve ends): every agent's new fat
+  // AABB (the list rebuild reads the pairs' two) and its final position (the nearest-neighbour sweep)
+  float4* const s_fn = reinterpret_cast<float4*>(s_tn);
+  float2* const s_pc = reinterpret_cast<float2*>(s_tn + 4 * W);
+  static_assert((sizeof(float4) + sizeof(float2)) * W <= sizeof(float) * 2 * TCAP, "s_fn and s_pc must fit in s_tn");
   uint32_t* const s_tm = s_pool.tm;
   uint32_t* const s_oldm = s_pool.oldm;
   // per-body touching edges when T > 64 TMW (no scalar DFS); Flock: in s_tm's words, which only
@@ -1909,6 +1898,7 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
 
   // ---- SynchronizeFixtures: fat-AABB update ------------------------------------
   float4 fn = fo;
+  bool contains = true;  // false: the proxy moves (b2BroadPhase::MoveProxy buffers it)
   if (act) {
     cx = s_c[lane].x;
     cy = s_c[lane].y;
@@ -1916,7 +1906,7 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
     const float c0x = p.x, c0y = p.y;
     const float lox = bmin(c0x - r, cx - r), loy = bmin(c0y - r, cy - r);
     const float hix = bmax(c0x + r, cx + r), hiy = bmax(c0y + r, cy + r);
-    const bool contains = fo.x <= lox && fo.y <= loy && hix <= fo.z && hiy <= fo.w;
+    contains = fo.x <= lox && fo.y <= loy && hix <= fo.z && hiy <= fo.w;
     if (!contains) {
       fn = make_float4(lox - kAabbExtension, loy - kAabbExtension, hix + kAabbExtension, hiy + kAabbExtension);
       const float dx = kAabbMultiplier * (cx - c0x), dy = kAabbMultiplier * (cy - c0y);
@@ -1929,63 +1919,57 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
       ns = 0.0f;
     }
   }
-  {
-    // per-agent record for the all-pairs sweep; lanes >= N hold a dummy whose AABB
-    // overlaps nothing and whose position is infinitely far away
-    PairRec r;
-    r.fn = act ? fn : make_float4(__builtin_inff(), __builtin_inff(), -__builtin_inff(), -__builtin_inff());
-    r.c = act ? make_float2(cx, cy) : make_float2(__builtin_inff(), __builtin_inff());
-    r.pad = make_float2(0.0f, 0.0f);
-    s_pj[lane] = r;
-  }
-  __syncthreads();  // s_pj and final s_c visible to every lane
+  // the proxies whose fat AABB was rewritten: exactly the move buffer of b2BroadPhase (lanes >= N
+  // and TDM bodies outside the physics step are never in it)
+  const unsigned long long movedm = __ballot(act && !contains);
+  // every agent's new fat AABB and final position; the lanes outside the physics step hold an AABB
+  // that overlaps nothing and a position infinitely far away
+  s_fn[lane] = act ? fn : make_float4(__builtin_inff(), __builtin_inff(), -__builtin_inff(), -__builtin_inff());
+  if constexpr (!kT) s_pc[lane] = act ? make_float2(cx, cy) : make_float2(__builtin_inff(), __builtin_inff());
+  __syncthreads();  // s_fn, s_pc and final s_c visible to every lane
   STAMP(9);
 
   // ---- contact set, new pairs, nearest neighbour ---------------------------------
   // The old list IS Ov(F_{t-1}), so only the new fat AABBs are tested here:
   //   world.contacts after the step = Ov(F_{t-1}) U Ov(F_t)        
   //   FindNewContacts creates        Ov(F_t) \ Ov(F_{t-1})
-  // Agent j's record arrives by LDS broadcast; each lane accumulates its own partner
-  // row one bit per record (2 VALU: compare into VCC, add-with-carry). The sweep is
-  // fully unrolled over NCAP >= N records (lanes >= N hold dummies that overlap
-  // nothing and are infinitely far), so j is a compile-time constant, and the AABB /
-  // distance differences run as packed float2 ops (each lane-wise result is the same
-  // IEEE op as scalar). The ballot + v_writelane form of the row costs 0.5% more.
+  // and of Ov(F_t) only the pairs with a moved proxy (moved_pairs): the others are in the old
+  // list. The nearest neighbour (Flock) takes the sweep over all NCAP >= N positions, fully
+  // unrolled, so j is a compile-time constant.
   const unsigned long long valid = livem;
-  SweepState sw;
-  sw.ov_lo = 0u;
-  sw.ov_hi = 0u;
-  sw.best = __builtin_inff();
-  sw.bj = lane == 0 ? 1 : 0;
-  if constexpr (NCAP == 64 && !kT) {  // two interleaved chains
-    constexpr int AH2 = 2 * kSweepAhead;  // records in flight (two per step)
-    SweepState2 s2;
-    s2.ov_lo = 0u;
-    s2.ov_hi = 0u;
-    s2.best_a = __builtin_inff();
-    s2.best_b = __builtin_inff();
-    s2.bj_a = lane == 0 ? 1 : 0;
-    s2.bj_b = 32;
-    SweepRec win[AH2];
+  float best = __builtin_inff();
+  int bj = lane == 0 ? 1 : 0;
+  if constexpr (!kT) {
+    const float4* const s_pc2 = reinterpret_cast<const float4*>(s_pc);
+    if constexpr (NCAP == 64) {  // two interleaved chains
+      NearState2 s2;
+      s2.best_a = __builtin_inff();
+      s2.best_b = __builtin_inff();
+      s2.bj_a = lane == 0 ? 1 : 0;
+      s2.bj_b = 32;
+      float4 win[2 * kNearAhead];
 #pragma unroll
-    for (int k = 0; k < AH2; ++k) win[k] = load_rec(s_pj, (k & 1) ? 32 + (k >> 1) : (k >> 1));
-    sweep2_step<0, AH2, SCAL>(s_pj, win, mk2(fn.x, fn.y), mk2(fn.z, fn.w), mk2(cx, cy), s2);
-    sw.ov_lo = s2.ov_lo;
-    sw.ov_hi = s2.ov_hi;
-    const bool upper = s2.best_b < s2.best_a;  // the lower half wins ties (lower indices)
-    sw.best = upper ? s2.best_b : s2.best_a;
-    sw.bj = upper ? s2.bj_b : s2.bj_a;
-  } else {
-    SweepRec win[kSweepAhead];
+      for (int k = 0; k < kNearAhead; ++k) {
+        win[2 * k] = s_pc2[k];
+        win[2 * k + 1] = s_pc2[16 + k];
+      }
+      near2_step<0, SCAL>(s_pc2, win, mk2(cx, cy), s2);
+      const bool upper = s2.best_b < s2.best_a;  // the lower half wins ties (lower indices)
+      best = upper ? s2.best_b : s2.best_a;
+      bj = upper ? s2.bj_b : s2.bj_a;
+    } else {
+      NearState s1;
+      s1.best = best;
+      s1.bj = bj;
+      float4 win[kNearAhead];
 #pragma unroll
-    for (int k = 0; k < kSweepAhead; ++k) win[k] = load_rec(s_pj, k);
-    sweep_step<0, NCAP, !kT>(s_pj, win, mk2(fn.x, fn.y), mk2(fn.z, fn.w), mk2(cx, cy), valid, lane, sw);
+      for (int k = 0; k < kNearAhead; ++k) win[k] = s_pc2[k];
+      near_step<0, NCAP>(s_pc2, win, mk2(cx, cy), s1);
+      best = s1.best;
+      bj = s1.bj;
+    }
   }
-  const float best = sw.best;
-  const int bj = sw.bj;
-  const uint32_t ov_lo = __builtin_bitreverse32(sw.ov_lo), ov_hi = __builtin_bitreverse32(sw.ov_hi);
-  unsigned long long myov = (((unsigned long long)ov_hi << 32) | ov_lo) & valid;
-  myov &= ~(1ull << lane);
+  const unsigned long long myov = moved_pairs(movedm, fn, lane) & valid & ~(1ull << lane);
   const unsigned long long oldm = (unsigned long long)s_oldm[2 * lane] | ((unsigned long long)s_oldm[2 * lane + 1] << 32);
   const bool coll = act && ((myov | oldm) != 0ull);
   const unsigned long long above = lane == 63 ? 0ull : (~0ull << (lane + 1));
@@ -2011,7 +1995,7 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
     const bool touch = (tbits >> c) & 1u;
     if (k < M) {
       const int a = ab & 0xffffu, b = ab >> 16;
-      keep = overlap(s_pj[a].fn, s_pj[b].fn);
+      keep = overlap(s_fn[a], s_fn[b]);
     }
     const unsigned long long mt = __ballot(touch), mk = __ballot(keep);
     const int trank = Tr + __popcll(mt & lt);
