@@ -20,21 +20,60 @@ def assert_state_equal(gs, os_, ctx=""):
                                       err_msg=f"{ctx} env {e} impulses")
 
 
-def f32_obs_mismatch(gpu_obs, oracle_obs64):
-    """Count float32 obs entries differing from the oracle's f64 obs rounded to f32."""
+# Observation layouts: which columns of the last axis are distances (or flags), angles, cos/sin.
+OBS_LAYOUTS = {
+    "flock_polar": dict(exact=(0, 2), angle=(1, 3), cs=()),        # (r, t) of the neighbour, of the target
+    "flock_cart": dict(exact=(0, 3), angle=(), cs=(1, 2, 4, 5)),   # (r, cos t, sin t) twice
+    "tdm": dict(exact=(0, 3), angle=(1, 2), cs=()),                # (r, t, p, is_ally) per slot
+}
+ANGLE_ATOL = 1e-14  # goldens.obs_close's angle tolerance on the float64 observations
+
+
+def flock_layout(obs):
+    """The layout name of a Flock observation array, from its width (4: polar, 6: cartesian)."""
+    return {4: "flock_polar", 6: "flock_cart"}[obs.shape[-1]]
+
+
+def _f32_ordinal(x):
+    """float32 -> int64, monotonic in the value (adjacent floats differ by 1; -0 and +0 coincide)."""
+    i = np.ascontiguousarray(x, np.float32).view(np.int32).astype(np.int64)
+    return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+
+
+def f32_obs_mismatch(gpu_obs, oracle_obs64, layout):
+    """Count float32 obs entries differing from the oracle's f64 obs rounded to f32; assert that
+    each of them is admissible for its column (layout: a key of OBS_LAYOUTS):
+
+    - distance and flag columns: at most 1 float32 ulp, nothing else;
+    - angle and cos/sin columns: at most 1 ulp (the double atan2 / cos / sin of the device and of
+      glibc round differently in rare cases), or at most 1e-14 absolute: `atan2 - angle` cancels
+      towards 0, where a float64 ulp of the operands is many float32 ulps of the difference;
+    - angle columns only: a sign flip where both values are within 2 float32 ulps of pi in magnitude,
+      the wrap at exactly +-pi (one ulp for each side's rounding)."""
+    cols = OBS_LAYOUTS[layout]
+    width = len(cols["exact"]) + len(cols["angle"]) + len(cols["cs"])
+    assert gpu_obs.dtype == np.float32 and gpu_obs.shape == oracle_obs64.shape and gpu_obs.shape[-1] == width, \
+        (layout, gpu_obs.dtype, gpu_obs.shape, oracle_obs64.shape)
     ref = oracle_obs64.astype(np.float32)
     d = gpu_obs != ref
     if not d.any():
         return 0
-    # tolerate 1-ulp differences (double atan2/cos/sin of ocml vs glibc round differently
-    # in rare cases); anything else is a real mismatch
-    ulp = np.abs(gpu_obs.view(np.int32).astype(np.int64) - ref.view(np.int32).astype(np.int64))
-    bad = d & (ulp > 1)
-    # angle wrap at exactly +-pi may flip sign: compare modulo 2pi
+    kg, kr = _f32_ordinal(gpu_obs), _f32_ordinal(ref)
+    ok = np.abs(kg - kr) <= 1
+    loose = np.zeros(gpu_obs.shape[-1], bool)
+    loose[list(cols["angle"] + cols["cs"])] = True
+    with np.errstate(invalid="ignore"):
+        ok |= loose & (np.abs(gpu_obs.astype(np.float64) - ref.astype(np.float64)) <= ANGLE_ATOL)
+    angle = np.zeros(gpu_obs.shape[-1], bool)
+    angle[list(cols["angle"])] = True
+    kpi = int(_f32_ordinal(np.float32(np.pi)).reshape(-1)[0])
+    ok |= angle & (np.signbit(gpu_obs) != np.signbit(ref)) & (np.abs(np.abs(kg) - kpi) <= 2) & (np.abs(np.abs(kr) - kpi) <= 2)
+    bad = d & ~ok
     if bad.any():
-        diff = np.abs(((gpu_obs.astype(np.float64) - ref + np.pi) % (2 * np.pi)) - np.pi)
-        bad &= diff > 1e-6
-    assert not bad.any(), f"{int(bad.sum())} obs entries off by more than 1 ulp"
+        idx = np.argwhere(bad)[:5]
+        rows = "; ".join(f"{tuple(int(v) for v in i)}: gpu {float(gpu_obs[tuple(i)])!r} ({int(gpu_obs[tuple(i)].view(np.uint32)):#010x})"
+                         f" ref {float(ref[tuple(i)])!r} ({int(ref[tuple(i)].view(np.uint32)):#010x})" for i in idx)
+        raise AssertionError(f"{int(bad.sum())} obs entries outside the {layout} tolerance: {rows}")
     return int(d.sum())
 
 

@@ -8,7 +8,8 @@ sin/cos(angle + pi/2). tools/trig_check.c enumerates every float32 angle |a| < 2
 requires every derived float32 value to equal glibc's; macm_action_trig gets there with
 a 17-entry table of glibc values (csrc/trig_fix.inc) at the inputs where its polynomial
 would round differently. Host and device builds agree bit for bit (tools/trig_gpu_check.hip
-prints the same digest on the GPU; profiles/r01/trig/)."""
+prints the same digest on the GPU, profiles/r01/trig/; tests/test_gpu_primitives.py compares the
+two builds on a stratified subset in every GPU run)."""
 import ctypes
 import math
 import os

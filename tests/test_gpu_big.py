@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from parity import assert_state_equal, f32_obs_mismatch
+from parity import assert_state_equal, f32_obs_mismatch, flock_layout
 from test_gpu_parity import check_rollout, make_pair, rand_actions
 
 pytestmark = pytest.mark.gpu
@@ -52,7 +52,7 @@ def test_big_world_rollout_trajectory_and_reset_envs():
         r = orc.step(acts[k])
         np.testing.assert_array_equal(traj["reward"][k].cpu().numpy(), r["reward"].astype(np.float32))
         np.testing.assert_array_equal(traj["nbr_id"][k].cpu().numpy(), r["nbr_id"])
-        f32_obs_mismatch(traj["obs"][k].cpu().numpy(), r["obs"])
+        f32_obs_mismatch(traj["obs"][k].cpu().numpy(), r["obs"], flock_layout(r["obs"]))
     assert_state_equal(vec.get_state(), orc.get_state(vec.world.C), "after the trajectory")
     mask = np.array([1, 0], np.uint8)
     vec.reset_envs(torch.from_numpy(mask).cuda())

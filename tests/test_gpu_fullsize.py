@@ -17,7 +17,7 @@ import pytest
 import torch
 
 from oracle import OracleTDM
-from parity import assert_state_equal, f32_obs_mismatch, oracle_for
+from parity import assert_state_equal, f32_obs_mismatch, flock_layout, oracle_for
 from test_gpu_tdm import assert_tdm_state_equal, random_actions
 
 pytestmark = pytest.mark.gpu
@@ -74,7 +74,7 @@ def flock_full(E, N, steps, targets=None, max_contacts=None, n_sample=4, seed=SE
             np.testing.assert_array_equal(rew[e:e + 1], r["reward"].astype(np.float32), err_msg=f"rew env {e} step {t}")
             np.testing.assert_array_equal(nbr[e:e + 1], r["nbr_id"], err_msg=f"nbr env {e} step {t}")
             np.testing.assert_array_equal(coll[e:e + 1], r["collided"], err_msg=f"coll env {e} step {t}")
-            f32_obs_mismatch(obs[e:e + 1], r["obs"])
+            f32_obs_mismatch(obs[e:e + 1], r["obs"], flock_layout(r["obs"]))
     assert vec.status() == 0
     assert int(vec.counters()[0]) == E * N * steps
     s = vec.get_state()
@@ -129,7 +129,7 @@ def test_c4_tdm_full_size_4096x2x16():
             np.testing.assert_array_equal(health[e:e + 1], r["health"], err_msg=f"health env {e} step {t}")
             np.testing.assert_array_equal(alive[e:e + 1], r["alive"], err_msg=f"alive env {e} step {t}")
             np.testing.assert_array_equal(mask[e:e + 1], r["mask"], err_msg=f"mask env {e} step {t}")
-            f32_obs_mismatch(obs[e:e + 1], r["obs"])
+            f32_obs_mismatch(obs[e:e + 1], r["obs"], "tdm")
     assert w.status() == 0
     s = w.get_state()
     check_contact_lists(s, N)
@@ -155,7 +155,7 @@ def check_sampled_final(vec, orcs, last, E, ctx):
         np.testing.assert_array_equal(rew[e:e + 1], r["reward"].astype(np.float32), err_msg=f"{ctx} rew env {e}")
         np.testing.assert_array_equal(nbr[e:e + 1], r["nbr_id"], err_msg=f"{ctx} nbr env {e}")
         np.testing.assert_array_equal(coll[e:e + 1], r["collided"], err_msg=f"{ctx} coll env {e}")
-        f32_obs_mismatch(obs[e:e + 1], r["obs"])
+        f32_obs_mismatch(obs[e:e + 1], r["obs"], flock_layout(r["obs"]))
 
 
 def test_c5_shard_driver_launch_form_2048x1024():

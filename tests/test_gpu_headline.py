@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 import torch
 
-from parity import assert_state_equal, f32_obs_mismatch, flock_bot, oracle_for
+from parity import assert_state_equal, f32_obs_mismatch, flock_bot, flock_layout, oracle_for
 
 pytestmark = pytest.mark.gpu
 
@@ -45,7 +45,7 @@ def check_last_outputs(vec, r):
     np.testing.assert_array_equal(vec.nbr_id.cpu().numpy(), r["nbr_id"])
     np.testing.assert_array_equal(vec.world.collided.cpu().numpy(), r["collided"])
     np.testing.assert_array_equal(vec.world.done.cpu().numpy(), r["done"])
-    f32_obs_mismatch(vec.obs.cpu().numpy(), r["obs"])
+    f32_obs_mismatch(vec.obs.cpu().numpy(), r["obs"], flock_layout(r["obs"]))
 
 
 def check_reward_sums(vec, rs):
@@ -112,7 +112,7 @@ def test_headline_trajectory_launch_all_envs_match_oracle():
         np.testing.assert_array_equal(rows["nbr_id"][j], r["nbr_id"], err_msg=f"nbr_id row {j}")
         np.testing.assert_array_equal(rows["collided"][j], r["collided"], err_msg=f"collided row {j}")
         np.testing.assert_array_equal(rows["done"][j], r["done"], err_msg=f"done row {j}")
-        f32_obs_mismatch(rows["obs"][j], r["obs"])
+        f32_obs_mismatch(rows["obs"][j], r["obs"], flock_layout(r["obs"]))
         tot += [E * N, int(r["collided"].sum()), int((r["reward"] > 0).sum()), int(r["done"].sum())]
         rs += pairwise_reward_sum(r["reward"])
     assert vec.status() == 0

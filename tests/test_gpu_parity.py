@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import goldens
-from parity import assert_state_equal, f32_obs_mismatch, oracle_for
+from parity import assert_state_equal, f32_obs_mismatch, flock_layout, oracle_for
 
 pytestmark = pytest.mark.gpu
 
@@ -33,10 +33,10 @@ def rand_actions(rng, E, N):
 
 
 def obs_check(gpu_obs, oracle_obs64, obs_f64, ctx):
-    """f32 obs: the oracle's f64 values rounded to f32 (<= 1 ulp, see parity.py);
+    """f32 obs: the oracle's f64 values rounded to f32 (<= 1 ulp; angles: see parity.f32_obs_mismatch);
     f64 obs: within a few f64 ulp (goldens.obs_close)."""
     if not obs_f64:
-        return f32_obs_mismatch(gpu_obs, oracle_obs64)
+        return f32_obs_mismatch(gpu_obs, oracle_obs64, flock_layout(gpu_obs))
     od = gpu_obs.shape[-1]
     for e in range(gpu_obs.shape[0]):
         assert goldens.obs_close(gpu_obs[e], oracle_obs64[e], od), f"obs {ctx} env {e}"

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import OracleTDM
-from parity import assert_state_equal, combat_bot, f32_obs_mismatch, oracle_for
+from parity import assert_state_equal, combat_bot, f32_obs_mismatch, flock_layout, oracle_for
 from test_gpu_tdm import assert_tdm_state_equal
 
 pytestmark = pytest.mark.gpu
@@ -44,7 +44,7 @@ def test_flock_reset_envs_continue_each_stream(N):
         o, nbr = orc.observe()
         m = mask.astype(bool)
         np.testing.assert_array_equal(vec.nbr_id.cpu().numpy()[m], nbr[m])
-        f32_obs_mismatch(vec.obs.cpu().numpy()[m], o[m])
+        f32_obs_mismatch(vec.obs.cpu().numpy()[m], o[m], flock_layout(o))
     vec.reset_envs()  # all
     orc.reset_envs()
     assert_state_equal(vec.get_state(), orc.get_state(vec.world.C), "reset all")

@@ -4,10 +4,13 @@ macm_world_reward_sums keeps one float64 total per env: each step's float32 rewa
 over the agent slots (flock_common.hpp block_pairwise_sum), added in step order. The host
 restatement is gym_macm.dist.pairwise_reward_sum; the total over envs is their sum in env order
 (gym_macm.dist.env_order_sum), which the multi-GPU path reproduces at any rank count
-(tests/test_distributed.py). Bar: bit-exact against the oracle's rewards (binary mode is an integer
-count, so the linear mode — values like 1 - d/35 — is what tests the order) in every launch form
-and step path: the wave kernel per step and in one rollout launch, the workgroup path with a
-number of waves that is not a power of two, the env slices on their own streams, the spill step,
+(tests/test_distributed.py). Bar: bit-exact against the oracle's rewards in every launch form and
+step path. These tests pin which rewards are summed, per env and per step, not the pairing order:
+binary mode is an integer count, and the linear mode's values like 1 - d/35 are float32 widened to
+float64, 24-bit significands of which 64 sum exactly whatever the order. The order itself
+(wave_pairwise_sum's DPP steps, block_pairwise_sum's zero padding) is tested on float64 values of
+mixed exponents in tests/test_gpu_primitives.py. The forms and paths: the wave kernel per step and
+in one rollout launch, the workgroup path with a number of waves that is not a power of two, the env slices on their own streams, the spill step,
 the trajectory form at the metric size (self-consistency with the rewards it returns) and the
 closed loop. Every tests/ rollout through test_gpu_parity.check_rollout checks the sums too, in
 binary mode as well, where the library reads an env's total from its counters (positive-reward minus

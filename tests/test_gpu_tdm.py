@@ -54,7 +54,7 @@ def check_obs(w, o_obs, o_mask, ctx):
         for e in range(w.E):
             assert tdm_obs_close(w.obs[e].cpu().numpy(), o_obs[e], o_mask[e]), f"obs {ctx} env {e}"
     else:
-        f32_obs_mismatch(w.obs.cpu().numpy(), o_obs)
+        f32_obs_mismatch(w.obs.cpu().numpy(), o_obs, "tdm")
 
 
 def check_rollout(w, orc, steps, policy, state_every=1):

@@ -42,7 +42,9 @@ def test_bad_buffers_raise(key, t):
 def test_pairwise_reward_sum_order():
     """gym_macm.dist.pairwise_reward_sum: the device's order (flock_common.hpp block_pairwise_sum) —
     float32 rewards as float64, pairwise over P = 64 * 2^ceil(log2(waves)) slots with +0.0 past N —
-    against a recursive restatement, at N that fill 1, 2, 3 -> 4 and 5 -> 8 waves."""
+    against a recursive restatement, at N that fill 1, 2, 3 -> 4 and 5 -> 8 waves. Rewards are float32:
+    their float64 sums are exact in any order, so this pins the padding and shape of the host function;
+    the device's pairing order is tested on order-sensitive float64 values in tests/test_gpu_primitives.py."""
     import numpy as np
     from gym_macm.dist import env_order_sum, pairwise_reward_sum
 
