@@ -727,8 +727,11 @@ __device__ __forceinline__ unsigned long long moved_pairs(unsigned long long mov
 
 // New-pair compaction in descending (a, b) order: lane a owns the bitmask of
 // partners b > a. Returns the total count; writes at most C entries.
+// stage_ab / stage_im (LDS, RCH * W entries; NULL: none): a copy of the entries below RCH * W, which a
+// carried rollout step hands to the next step in registers (StepCarry).
 __device__ __forceinline__ int write_new_pairs(int lane, unsigned long long newmask, uint32_t* ocab,
-                                               float2* ocimp, int C) {
+                                               float2* ocimp, int C, uint32_t* stage_ab = nullptr,
+                                               float2* stage_im = nullptr) {
   const int cnt = __popcll(newmask);
   const int pre = wave_prefix_sum(cnt);  // sum over lanes <= lane
   const int total = __builtin_amdgcn_readlane(pre, W - 1);
@@ -740,6 +743,10 @@ __device__ __forceinline__ int write_new_pairs(int lane, unsigned long long newm
     if (w < C) {
       st_g<kState>(ocab + w, (uint32_t)lane | ((uint32_t)j << 16));
       st_g<kState>(ocimp + w, make_float2(0.0f, 0.0f));
+      if (stage_ab && w < RCH * W) {
+        stage_ab[w] = (uint32_t)lane | ((uint32_t)j << 16);
+        stage_im[w] = make_float2(0.0f, 0.0f);
+      }
     }
     ++w;
   }
@@ -862,6 +869,26 @@ __device__ __forceinline__ void tdm_tail_row(const StepParams& P, const WorldBuf
   __syncthreads();  // the next row's snapshot overwrites s_c, s_ang and the stage
 }
 
+// What a Flock rollout's wave keeps in registers from one step to the next (env_rollout_w64, CARRY):
+// exactly the values the next step's up-front loads would return, each taken from what this step
+// stores, so a carried step starts without a global load and the step before it need not wait for
+// its stores. The step still stores everything, so global memory after any step is what a
+// one-step launch leaves. `valid` (wave-uniform) is false at a launch's first step, after a spill
+// step, a raised status bit or a list longer than the RCH register chunks: the next step then loads
+// as a one-step launch does, behind the workgroup fence that the rollout loop takes in that case.
+struct StepCarry {
+  bool valid;
+  float2 p, v, tg;
+  float ang, slp;
+  float4 fat;
+  uint32_t rab[RCH];  // the list's first RCH chunks, handed over through LDS (lane-indexed again)
+  float2 rim[RCH];
+  // the next step's actions, loaded while this step runs and decoded only by the next step (so
+  // nothing waits for them here): discrete a0 | a1 << 8 and a2, or the bits of the continuous (x, y)
+  uint32_t ar0, ar1;
+  int M, step_count;  // wave-uniform
+};
+
 // MODE kFlock: Flock.step. MODE kTdm: TDM.step (combat.py:104-184) — the same
 // physics with alive masks, plus melee ray casts, health, deaths and the full
 // relative observation; `TP`/`TB` are unused for Flock.
@@ -869,13 +896,18 @@ __device__ __forceinline__ void tdm_tail_row(const StepParams& P, const WorldBuf
 // resident together (the unrolled sweep would otherwise hoist every LDS record).
 // The body of one step of env blockIdx.x, inlined into the one-step kernel (env_step_w64) and
 // the multi-step kernel (env_rollout_w64); its LDS arrays are the kernel's.
-template <int MODE, int NCAP, typename OT, bool SCAL = false>
+// CARRY (Flock rollouts with given actions): `carry` is in/out (StepCarry); `actions_next` is the next
+// step's actions, loaded into it while this step runs (NULL at a launch's last step: there is no row
+// to read).
+template <int MODE, int NCAP, typename OT, bool SCAL = false, bool CARRY = false>
 __device__ __attribute__((always_inline)) inline void step_w64_body(
     const StepParams& P, const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur,
     const void* __restrict__ actions, OT* __restrict__ obs, int32_t* __restrict__ nbr_out,
     float* __restrict__ rew_out, uint8_t* __restrict__ coll_out, uint8_t* __restrict__ done_out,
-    const int e = blockIdx.x, const int lane = threadIdx.x, TailObs* tl = nullptr) {
+    const int e = blockIdx.x, const int lane = threadIdx.x, TailObs* tl = nullptr, StepCarry* carry = nullptr,
+    const void* actions_next = nullptr) {
   constexpr bool kT = MODE == kTdm;
+  static_assert(!CARRY || !kT, "the carried step is Flock's");
 #ifdef MACM_TIMELINE
   const unsigned long long tl_rt0 = __builtin_amdgcn_s_memrealtime(), tl_c0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -951,15 +983,21 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
   // ---- every global load the step needs, issued up front ---------------------
   const uint32_t* cab = B.cab[cur] + (size_t)e * C;
   const float2* cimp = B.cimp[cur] + (size_t)e * C;
-  const int step_count = B.step_count[e];
-  const int M = B.ccount[cur][e];
+  // a carried step (wave-uniform) takes them from the step before instead (StepCarry)
+  bool carried = false;
+  if constexpr (CARRY) carried = carry->valid;
+  int step_count = 0, M = 0;
+  if (!carried) {
+    step_count = B.step_count[e];
+    M = B.ccount[cur][e];
+  }
   float2 p = make_float2(0.0f, 0.0f), v = make_float2(0.0f, 0.0f), tg = make_float2(0.0f, 0.0f);
   float ang = 0.0f, slp = 0.0f;
   float4 fo = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   int a0 = 1, a1 = 1, a2 = 1, a3 = 0;
   float ax = 0.0f, ay = 0.0f;
   double hp = 0.0, cda = 0.0, cdm = 0.0;  // TDM: health, cooldown_atk, cooldown_mov_penalty
-  if (act) {
+  if (act && !carried) {
     p = B.pos[ag];
     v = B.vel[ag];
     ang = B.angle[ag];
@@ -994,7 +1032,8 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
   int2 lis = make_int2(0, -1);
   int win_prev = -1;
   uint8_t done_prev = 0;
-  if (lane == 0) {
+  // (CARRY: lane 0 loads its values where they are used, below: the same lane stored them)
+  if (lane == 0 && !CARRY) {
     time_passed = B.time_passed[e];
     st_prev = B.status[e];
     if constexpr (kT) {
@@ -1017,9 +1056,31 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
     const int k = c * W + lane;
     rab[c] = 0u;
     rim[c] = make_float2(0.0f, 0.0f);
-    if (k < M) {
+    if (k < M) {  // (carried: M is still 0 here)
       rab[c] = cab[k];
       rim[c] = cimp[k];
+    }
+  }
+  if constexpr (CARRY) {
+    if (carried) {
+      step_count = carry->step_count;
+      M = carry->M;
+      p = carry->p;
+      v = carry->v;
+      tg = carry->tg;
+      ang = carry->ang;
+      slp = carry->slp;
+      fo = carry->fat;
+      a0 = (int)(carry->ar0 & 0xffu);
+      a1 = (int)(carry->ar0 >> 8);
+      a2 = (int)carry->ar1;
+      ax = __uint_as_float(carry->ar0);
+      ay = __uint_as_float(carry->ar1);
+#pragma unroll
+      for (int c = 0; c < RCH; ++c) {
+        rab[c] = carry->rab[c];
+        rim[c] = carry->rim[c];
+      }
     }
   }
   s_c[lane] = p;
@@ -1238,6 +1299,12 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
     // memory yet, so it starts from the untouched start-of-step state; this wave returns after it.
     // (The scalar DFS of T <= 64 TMW has no degree cap: it walks bit masks.)
     if (touch_over || (!fast_dfs && __builtin_amdgcn_ballot_w64(deg > DEG) != 0ull) || P.force_spill) {
+      if constexpr (CARRY) {
+        // the spill step reads the state from global memory and writes it itself: the stores of the
+        // carried step before this one must have completed, and the next step loads again
+        if (carried) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        carry->valid = false;
+      }
       spill::step_env<OT, true>(P, B, e, cur, actions, obs, nbr_out, rew_out, coll_out, done_out,
                                 reinterpret_cast<unsigned char*>(&s_pool));
       return;
@@ -1293,6 +1360,24 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
   const unsigned long long hasdeg = __ballot(act && deg > 0);
   __syncthreads();
   STAMP(3);
+  if constexpr (CARRY) {
+    // The next step's actions: a new address every step, so they come from HBM; loaded here, and
+    // kept undecoded, they are in flight while the chain runs.
+    const bool discrete = P.action_mode == MACM_ACTION_DISCRETE;
+    carry->ar0 = discrete ? 0x0101u : 0u;  // lanes >= N: (1, 1, 1) / (0.0f, 0.0f), as a loading step
+    carry->ar1 = discrete ? 1u : 0u;
+    if (actions_next && act) {
+      if (discrete) {
+        const uint8_t* a = (const uint8_t*)actions_next + ag * 3;
+        carry->ar0 = (uint32_t)a[0] | ((uint32_t)a[1] << 8);
+        carry->ar1 = a[2];
+      } else {
+        const uint2 c = ((const uint2*)actions_next)[ag];
+        carry->ar0 = c.x;
+        carry->ar1 = c.y;
+      }
+    }
+  }
   // The serial Box2D chain (DFS, Gauss-Seidel, position passes) is a latency chain; the
   // waves sharing this SIMD run throughput phases (sweep, obs) that can fill its gaps.
   // Raising the issue priority of a wave that has touching contacts while it walks the
@@ -1976,10 +2061,31 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
   const unsigned long long newmask = act ? (myov & ~oldm & above) : 0ull;
   STAMP(10);
 
+  if constexpr (CARRY) {
+    // Lane 0's per-env values, needed in the step's last lines only: loaded here rather than
+    // carried. Lane 0 itself stored them a step ago (a lane reads its own stores in order, no
+    // fence needed), and their registers are free during the chain and the sweep.
+    if (lane == 0) {
+      time_passed = B.time_passed[e];
+      st_prev = B.status[e];
+      const ulonglong2* ec = reinterpret_cast<const ulonglong2*>(B.env_counters + (size_t)e * 4);
+      const ulonglong2 c01 = ec[0], c23 = ec[1];
+      ctr[0] = c01.x;
+      ctr[1] = c01.y;
+      ctr[2] = c23.x;
+      ctr[3] = c23.y;
+    }
+  }
   // ---- next ordered list: new pairs (desc) ++ surviving old pairs --------------
   uint32_t* ocab = B.cab[nxt] + (size_t)e * C;
   float2* ocimp = B.cimp[nxt] + (size_t)e * C;
-  const int nnew = write_new_pairs(lane, newmask, ocab, ocimp, C);
+  // Carried step: the entries below RCH * W also go to LDS by rank, over s_tab and s_tm (both dead
+  // since the position solve), and come back lane-indexed as the next step's register chunks.
+  uint32_t* const stage_ab = CARRY ? s_tab : nullptr;
+  float2* const stage_im = CARRY ? reinterpret_cast<float2*>(s_tm) : nullptr;
+  static_assert(sizeof(uint32_t) * RCH * W <= sizeof(s_pool.tab), "the staged entries must fit in s_tab");
+  static_assert(!CARRY || sizeof(float2) * RCH * W <= sizeof(s_pool.tm), "the staged impulses must fit in s_tm");
+  const int nnew = write_new_pairs(lane, newmask, ocab, ocimp, C, stage_ab, stage_im);
   int kept = 0, Tr = 0;
   for (int c = 0; c * W < M; ++c) {
     const int k = c * W + lane;
@@ -2009,6 +2115,12 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
         if (touch && trank < TCAP) l = make_float2(s_tln[trank], s_tlt[trank]);
         st_g<kState>(ocab + w, ab);
         st_g<kState>(ocimp + w, l);
+        if constexpr (CARRY) {
+          if (w < RCH * W) {
+            stage_ab[w] = ab;
+            stage_im[w] = l;
+          }
+        }
       }
     }
   }
@@ -2141,6 +2253,33 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
       if (P.reward_mode == MACM_REWARD_LINEAR) add_reward_sum(B, e, rsum);
     }
   }
+  if constexpr (CARRY) {
+    // ---- the next step's start-of-step values, from what this step stored --------
+    // (lanes >= N: values that no lane reads, as the zeros a loading step starts them from)
+    carry->p = make_float2(cx, cy);
+    carry->v = make_float2(vx, vy);
+    carry->ang = ang;
+    carry->fat = fn;
+    carry->slp = ns;
+    carry->tg = tg;
+    carry->M = total;
+    carry->step_count = step_count + 1;
+    __syncthreads();  // the staged list entries, written by rank, are read by index
+#pragma unroll
+    for (int c = 0; c < RCH; ++c) {
+      const int k = c * W + lane;
+      carry->rab[c] = 0u;
+      carry->rim[c] = make_float2(0.0f, 0.0f);
+      if (k < total) {
+        carry->rab[c] = stage_ab[k];
+        carry->rim[c] = stage_im[k];
+      }
+    }
+    // The next step must load (and this one's stores complete first: the rollout loop fences) when
+    // the list has chunks beyond the register ones, which come from global memory. A step that
+    // raises a status bit ends the carry too: the launch is about to be reported as failed.
+    carry->valid = total <= RCH * W && !(mst1 | mst2 | mst4);
+  }
   STAMP(13);
 #ifdef MACM_TIMELINE
   {
@@ -2171,7 +2310,8 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
 // counters accumulated. Each env's wave runs its own steps back to back, so no env waits at a
 // launch boundary for the slowest env of the batch. Every step reads only what this wave
 // wrote in the step before: a workgroup-scope fence completes its stores before the next step's
-// loads; the barrier orders the LDS reuse. This part is compiled in its own translation unit
+// loads; the barrier orders the LDS reuse. (Flock rollouts with given actions keep that state in
+// registers instead and fence only before a step that loads: StepCarry.) This part is compiled in its own translation unit
 // (flock_rollout_w64.hip, -mllvm -disable-machine-licm): with the step inside a loop, machine
 // LICM hoists the f64 polynomial constants of the trig and atan2 code out of it and the
 // register allocator spills them (327 VGPRs of spills; none without the hoisting).
@@ -2199,9 +2339,9 @@ struct RolloutArgs {  // the kernel's only argument (kernarg offset 0)
   // step k reading row k and writing row k + 1) advances one row per step
   int traj;
   // A balanced launch steps envs order[sched_off + blockIdx.x]; sched_off is 0 since the solo split
-  // was removed (round 6), and kept with `reserved` so the kernel's argument layout (and with it its
-  // register allocation) stays the measured one: without them the driver window ran 1.1% slower, with
-  // them 0.3% (in noise) against the library before the removal (profiles/r06/abtests/cleanup/).
+  // was removed (round 6), and kept so that the kernel's argument layout (and with it its register
+  // allocation) stays the measured one: without it the driver window ran 1.1% slower, with it 0.3%
+  // (in noise) against the library before the removal (profiles/r06/abtests/cleanup/).
   int sched_off;
   // the tail observation (TailObs; TDM trajectory rollouts, macm_capi tdm_tail_obs): its counters and
   // ready words, and this launch's tag (0: off; blocks beyond n_envs then do not exist)
@@ -2209,6 +2349,10 @@ struct RolloutArgs {  // the kernel's only argument (kernarg offset 0)
   unsigned int tail_tag;
   int tail_k0;  // the first step observed in the tail (0: all); the steps before observe in the step
 };
+// Carried Flock rollouts (CARRY) only: this bit of RolloutArgs::cur is MACM_DEBUG_ROLLOUT_RELOAD, every
+// step loads its state and waits for the stores of the step before, as a rollout without the carry.
+// (Not a field of its own: the argument layout of the other rollout kernels stays the measured one.)
+constexpr int kRollReloadBit = 2;
 
 // [K, ...] row k of an output (trajectory form); NULL stays NULL
 template <typename T>
@@ -2260,7 +2404,11 @@ __global__ __launch_bounds__(1024) void rollout_sched(const uint32_t* __restrict
 
 // A balanced rollout's heaviest envs in waves that own their SIMD, on a stream of their own ("solo"
 // waves, round 5), measured slower and were removed in round 6 (profiles/r05/abtests/).
-template <int MODE, int NCAP, typename OT, bool SCAL = false>
+// CARRY (Flock, actions given: launch_roll): the wave keeps its env's state, the first RCH list chunks
+// and the next step's actions in registers between steps (StepCarry) and takes the fence only before a
+// step that has to load. The closed loop (the bot reads the obs the step just stored) and TDM run
+// the instantiations without it.
+template <int MODE, int NCAP, typename OT, bool SCAL = false, bool CARRY = false>
 __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env_rollout_w64(RolloutArgs<OT> A0) {
   const int nsteps = A0.nsteps;
   const bool bal = A0.B.sched && nsteps >= kRollBalanceMinSteps;  // as in launch_roll
@@ -2282,6 +2430,7 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
   tl.r_end = 0;
   tl.nq = nq;
   const int ksteps = phys ? nsteps : 0;
+  StepCarry cy{};  // CARRY; not valid: the first step loads
   for (int k = 0; k < ksteps; ++k) {
     // each step reads its parameters from the kernel arguments afresh, through a pointer the
     // compiler cannot see through, so nothing derived from them stays live across the loop
@@ -2314,26 +2463,39 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
     int sl = (int)threadIdx.x;
     if constexpr (MODE == kTdm) asm volatile("" : "+v"(sl));
     tl.k = k - A0.tail_k0;
-    step_w64_body<MODE, NCAP, OT, SCAL>(A.P, A.B, A.TP, TB, A.cur ^ (k & 1),
-                                        pol_in ? pol_in : static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride,
-                                        obs, traj_row(A.nbr_out, kr, EN), traj_row(A.rew_out, kr, EN),
-                                        traj_row(A.coll_out, kr, EN), traj_row(A.done_out, kr, (size_t)A.P.n_envs),
-                                        env, sl, MODE == kTdm ? &tl : nullptr);
-    // the next step reads only what this wave wrote: workgroup scope (this CU's L1 and its XCD's L2)
-    // suffices; agent scope would write back and invalidate the L2 every step (5x slower, measured)
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __syncthreads();
-    if (pol_in) {  // every agent row, as the bots kernel over all E x N rows
-      uint8_t* const pol_out = A.traj ? pol_in + EN * abytes : pol_in;
-      if (lane < N) {
-        const size_t row = (size_t)env * N + lane;
-        if constexpr (MODE == kTdm)
-          bot_combat_row(obs + row * (N - 1) * 4, TB.mask_out + row * (N - 1), N, pol_out + row * 4);
-        else
-          bot_flock_row(obs + row * od, (int)od, pol_out + row * 3);
-      }
+    if constexpr (CARRY) {
+      const unsigned char* const act_k = static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride;
+      step_w64_body<MODE, NCAP, OT, SCAL, true>(A.P, A.B, A.TP, TB, (A.cur ^ k) & 1, act_k, obs,
+                                                traj_row(A.nbr_out, kr, EN), traj_row(A.rew_out, kr, EN),
+                                                traj_row(A.coll_out, kr, EN), traj_row(A.done_out, kr, (size_t)A.P.n_envs),
+                                                env, sl, nullptr, &cy, k + 1 < ksteps ? act_k + A.astride : nullptr);
+      if (A.cur & kRollReloadBit) cy.valid = false;
+      // only a step that loads reads what this wave stored (workgroup scope: below); the barrier
+      // orders the LDS reuse
+      if (!cy.valid) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      __syncthreads();
+    } else {
+      step_w64_body<MODE, NCAP, OT, SCAL>(A.P, A.B, A.TP, TB, A.cur ^ (k & 1),
+                                          pol_in ? pol_in : static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride,
+                                          obs, traj_row(A.nbr_out, kr, EN), traj_row(A.rew_out, kr, EN),
+                                          traj_row(A.coll_out, kr, EN), traj_row(A.done_out, kr, (size_t)A.P.n_envs),
+                                          env, sl, MODE == kTdm ? &tl : nullptr);
+      // the next step reads only what this wave wrote: workgroup scope (this CU's L1 and its XCD's L2)
+      // suffices; agent scope would write back and invalidate the L2 every step (5x slower, measured)
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __syncthreads();
+      if (pol_in) {  // every agent row, as the bots kernel over all E x N rows
+        uint8_t* const pol_out = A.traj ? pol_in + EN * abytes : pol_in;
+        if (lane < N) {
+          const size_t row = (size_t)env * N + lane;
+          if constexpr (MODE == kTdm)
+            bot_combat_row(obs + row * (N - 1) * 4, TB.mask_out + row * (N - 1), N, pol_out + row * 4);
+          else
+            bot_flock_row(obs + row * od, (int)od, pol_out + row * 3);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __syncthreads();
+      }
     }
   }
   if constexpr (MODE == kTdm) {
@@ -2379,7 +2541,7 @@ static void launch_roll(int nsteps, unsigned long long astride, int traj, hipStr
                         const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur, const void* actions,
                         void* obs, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done,
                         unsigned long long* tail_ctl = nullptr, unsigned tail_tag = 0u, int tail_workers = 0,
-                        int tail_k0 = 0) {
+                        int tail_k0 = 0, int reload = 0) {
   // astride == 0: closed loop, `actions` is the bots' action buffer (macm_world_rollout_bots)
   uint8_t* pol = astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(actions)) : nullptr;
   const bool bal = B.sched && nsteps >= kRollBalanceMinSteps;
@@ -2394,6 +2556,13 @@ static void launch_roll(int nsteps, unsigned long long astride, int traj, hipStr
   RolloutArgs<OT> A{P, B, TP, TB, actions, (OT*)obs, nbr, rew, coll, done, astride, cur, nsteps, pol, traj, 0,
                     tail_ctl, tail_tag, tail_tag ? tail_k0 : 0};
   const int blocks = P.n_envs + (tail_tag ? tail_workers : 0);
+  if constexpr (MODE == kFlock) {
+    if (!pol) {  // actions given: the carried step
+      if (reload) A.cur |= kRollReloadBit;
+      hipLaunchKernelGGL((env_rollout_w64<MODE, NCAP, OT, SCAL, true>), dim3(blocks), dim3(W), 0, s, A);
+      return;
+    }
+  }
   hipLaunchKernelGGL((env_rollout_w64<MODE, NCAP, OT, SCAL>), dim3(blocks), dim3(W), 0, s, A);
 }
 
@@ -2407,23 +2576,27 @@ hipError_t launch_env_order(const uint32_t* ccount, uint32_t* order, int E, int 
 
 hipError_t launch_rollout_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
                               bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
-                              int nsteps, unsigned long long astride, int traj) {
+                              int nsteps, unsigned long long astride, int traj, int reload) {
   const TdmParams TP{};
   const TdmBuffers TB{};
   const bool small = P.n_agents <= 32;
   if (obs_f64) {
     if (small)
-      launch_roll<kFlock, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done);
+      launch_roll<kFlock, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
+                                     nullptr, 0u, 0, 0, reload);
     else
-      launch_roll<kFlock, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done);
+      launch_roll<kFlock, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
+                                     nullptr, 0u, 0, 0, reload);
   } else {
     if (small)
-      launch_roll<kFlock, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done);
+      launch_roll<kFlock, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
+                                     nullptr, 0u, 0, 0, reload);
     else if (P.n_envs >= kScalarSweepMinEnvs)
       launch_roll<kFlock, 64, float, true>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll,
-                                           done);
+                                           done, nullptr, 0u, 0, 0, reload);
     else
-      launch_roll<kFlock, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done);
+      launch_roll<kFlock, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
+                                     nullptr, 0u, 0, 0, reload);
   }
   return hipGetLastError();
 }

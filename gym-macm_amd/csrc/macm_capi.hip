@@ -20,7 +20,7 @@ hipError_t launch_step_w64(const StepParams& P, const WorldBuffers& B, int cur, 
                            bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s);
 hipError_t launch_rollout_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
                               bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
-                              int nsteps, unsigned long long astride, int traj);
+                              int nsteps, unsigned long long astride, int traj, int reload);
 hipError_t launch_init_w64(const StepParams& P, const WorldBuffers& B, int cur, void* obs, bool obs_f64,
                            int32_t* nbr, const uint8_t* mask, hipStream_t s);
 hipError_t launch_observe_w64(const StepParams& P, const WorldBuffers& B, void* obs, bool obs_f64, int32_t* nbr,
@@ -106,6 +106,7 @@ struct macm_world {
   bool ho_tried = false;
   int slots_alloc = 0;  // spill working-set slots allocated (== E: one per env)
   int pool0 = 0;        // B.sp_pool as created (0: one slot per env), restored by set_debug
+  int roll_reload = 0;  // MACM_DEBUG_ROLLOUT_RELOAD: wave rollouts load and fence every step
 };
 
 struct macm_tdm {
@@ -861,7 +862,7 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
            : (unsigned long long)w->P.n_envs * w->P.n_agents * (mode == 0 ? 3 * sizeof(uint8_t) : 2 * sizeof(float));
   if (w->wave) {  // one launch; astride 0: the closed-loop form of the rollout kernel
     HIP_TRY(launch_rollout_w64(w->P, w->B, w->cur, actions, out->obs, w->cfg.obs_f64 != 0, out->nbr_id, out->reward,
-                               out->collided, out->done, s, n_steps, astride, traj ? 1 : 0));
+                               out->collided, out->done, s, n_steps, astride, traj ? 1 : 0, w->roll_reload));
     if (n_steps & 1) w->cur ^= 1;
     return MACM_OK;
   }
@@ -1133,12 +1134,14 @@ int macm_world_set_debug(macm_world* w, int32_t flags) {
   if (!w) return fail(MACM_E_INVALID, "world is NULL");
   const int pool = (flags & MACM_DEBUG_SPILL_POOL) ? (flags >> 8) : 0;
   flags &= 0xff;
-  if (flags & ~(MACM_DEBUG_FORCE_SPILL | MACM_DEBUG_SWEEP_CELLS | MACM_DEBUG_SWEEP_ALL_PAIRS | MACM_DEBUG_SPILL_POOL | MACM_DEBUG_SPILL_FAIL))
+  if (flags & ~(MACM_DEBUG_FORCE_SPILL | MACM_DEBUG_SWEEP_CELLS | MACM_DEBUG_SWEEP_ALL_PAIRS | MACM_DEBUG_SPILL_POOL | MACM_DEBUG_SPILL_FAIL |
+                MACM_DEBUG_ROLLOUT_RELOAD))
     return fail(MACM_E_INVALID, "unknown debug flag");
   if ((flags & MACM_DEBUG_SWEEP_CELLS) && (flags & MACM_DEBUG_SWEEP_ALL_PAIRS))
     return fail(MACM_E_INVALID, "SWEEP_CELLS and SWEEP_ALL_PAIRS exclude each other");
   if (int rc = set_spill_pool(w, flags, pool)) return rc;
   w->P.force_spill = (flags & MACM_DEBUG_FORCE_SPILL) ? 1 : 0;
+  w->roll_reload = (flags & MACM_DEBUG_ROLLOUT_RELOAD) ? 1 : 0;
   w->P.sweep = (flags & MACM_DEBUG_SWEEP_CELLS) ? 1 : (flags & MACM_DEBUG_SWEEP_ALL_PAIRS) ? 2 : 0;
   return MACM_OK;
 }

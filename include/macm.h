@@ -88,8 +88,10 @@ enum {
   MACM_DEBUG_SWEEP_ALL_PAIRS = 4, /* N > 64: all-pairs pair sweep at any N                        */
   MACM_DEBUG_SPILL_POOL = 8,      /* the spill working set as a pool of (flags >> 8) slots, at most
                                      the slots allocated (pooled-slot tests at small E)            */
-  MACM_DEBUG_SPILL_FAIL = 16      /* no spill slot is ever free: every env that needs the spill step
+  MACM_DEBUG_SPILL_FAIL = 16,     /* no spill slot is ever free: every env that needs the spill step
                                      is left unstepped with MACM_ST_SPILL_WAIT (ABI 8 test hook)   */
+  MACM_DEBUG_ROLLOUT_RELOAD = 32  /* wave rollouts: every step loads its state from global memory
+                                     behind a fence, none is carried in registers (A/B, tests)     */
 };
 
 /*
