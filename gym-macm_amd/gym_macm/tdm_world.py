@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .world import _ptr, check_traj
+from .world import _ptr, check_seed_range, check_traj
 
 
 def tdm_config(n_agents=(1, 1), obs_f64=False, fresh_raycast=False, decay_mov_penalty=False, validate_actions=False,
@@ -97,8 +97,11 @@ class TdmWorld:
         return self.obs, self.mask, self.health, self.alive, self.done, self.winner
 
     def reset(self, seed: int, env_offset: int = 0):
-        """Env e := TDM(...) after random.seed(seed + env_offset + e); writes the initial obs."""
-        _abi.check(self.L.macm_tdm_reset(self.h, int(seed), int(env_offset), ctypes.byref(self._out),
+        """Env e := TDM(...) after random.seed(seed + env_offset + e); writes the initial obs.
+        ValueError when seed < 0, or when an env's seed seed + env_offset + e is negative or 2**64 or
+        more (world.check_seed_range: the C-ABI cannot honour random.seed's meaning there)."""
+        seed, env_offset = check_seed_range(seed, env_offset, self.E)
+        _abi.check(self.L.macm_tdm_reset(self.h, seed, env_offset, ctypes.byref(self._out),
                                          self._stream()), "macm_tdm_reset")
         return self.outputs()
 

@@ -10,7 +10,10 @@ launch per step, with actions and outputs as device tensors:
 Env e is the reference env constructed after ``random.seed(seed + env_offset + e)``;
 each env keeps that stream on the device, so ``reset_envs(mask)`` / ``autoreset=True``
 start new episodes exactly as the env's own ``reset()`` would draw them.
-shard a job over GPUs by giving each rank its contiguous ``env_offset``.
+``seed`` must be >= 0 and every env's seed ``seed + env_offset + e`` must lie in [0, 2**64): the
+C-ABI cannot honour ``random.seed``'s meaning outside it (a negative seed's absolute value, keys of
+three or more words), so the constructor and ``reset`` raise ValueError there (World.reset).
+Shard a job over GPUs by giving each rank its contiguous ``env_offset``.
 Settings keyword arguments are the reference's (flockSettings, settings.py:110-146).
 Returned tensors are views of buffers reused by the next call.
 """

@@ -19,6 +19,26 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def check_seed_range(seed, env_offset, n_envs) -> tuple:
+    """(seed, env_offset) as ints, after checking that every env's seed can be honoured: env e is the
+    reference env after ``random.seed(seed + env_offset + e)``, and the C-ABI takes seed as uint64_t and
+    env_offset as int64_t. CPython seeds a negative int by its absolute value and an int of 2**64 or more
+    by a key of three or more words; passed on, either would be wrapped modulo 2**64 into another env's
+    seed without a word. Raises ValueError when seed < 0, when seed or env_offset does not fit its C
+    type, or when seed + env_offset (env 0) is negative or seed + env_offset + n_envs - 1 (the last env)
+    is 2**64 or more."""
+    seed, env_offset, n_envs = int(seed), int(env_offset), int(n_envs)
+    if seed < 0:
+        raise ValueError(f"seed must be >= 0 (random.seed takes a negative seed's absolute value; pass abs(seed)), "
+                         f"got {seed}")
+    if seed >= 1 << 64 or not -(1 << 63) <= env_offset < 1 << 63:
+        raise ValueError(f"seed must be below 2**64 and env_offset within int64, got {seed} and {env_offset}")
+    lo, hi = seed + env_offset, seed + env_offset + n_envs - 1
+    if lo < 0 or hi >= 1 << 64:
+        raise ValueError(f"the envs' seeds seed + env_offset + e must lie in [0, 2**64): they span [{lo}, {hi}]")
+    return seed, env_offset
+
+
 def check_traj(traj: dict, spec: dict, K: int, device, keys) -> list:
     """The caller's trajectory buffers in `keys` order (None where absent), each checked against
     spec[key] = (dtype, per-step shape) before any kernel writes K rows into it: a buffer of the
@@ -105,8 +125,11 @@ class World:
 
     # -- lifecycle ---------------------------------------------------------
     def reset(self, seed: int, env_offset: int = 0):
-        """Env e := Flock(...) after random.seed(seed + env_offset + e); writes the initial obs."""
-        _abi.check(self.L.macm_world_reset(self.h, int(seed), int(env_offset), ctypes.byref(self._out_obs),
+        """Env e := Flock(...) after random.seed(seed + env_offset + e); writes the initial obs.
+        ValueError when seed < 0, or when an env's seed seed + env_offset + e is negative or 2**64 or
+        more (check_seed_range: the C-ABI cannot honour random.seed's meaning there)."""
+        seed, env_offset = check_seed_range(seed, env_offset, self.E)
+        _abi.check(self.L.macm_world_reset(self.h, seed, env_offset, ctypes.byref(self._out_obs),
                                            self._stream()), "macm_world_reset")
         self.done.zero_()
         return self.obs, self.nbr_id

@@ -223,6 +223,12 @@ typedef struct macm_tdm_state {
  * cos t, sin t, target r, cos t, sin t). Matches Flock.get_obs node order
  * (mvmnt.py:197-220): node 0 = closest agent (type 0, id = nbr_id), node 1 =
  * the agent's target (type 1, id = N).
+ *
+ * Alignment (macm_tdm_outputs too): obs must be 16-byte aligned, the kernels store a polar float32 row
+ * and every TDM slot as one 16-byte vector (float64: two); every other field needs its element type's
+ * alignment only (a TDM mask that is 16-byte aligned lets the tail observation store it in 16-byte
+ * pieces, any other is stored by bytes). A kernel writes only inside the [E, ...] (trajectory form:
+ * [n_steps, E, ...]) extent of the fields that are set.
  */
 typedef struct macm_outputs {
   void* obs;        /* [E, N, OD] float32 or float64 (config.obs_f64)          */
@@ -322,6 +328,10 @@ int macm_world_info_get(const macm_world* w, macm_world_info* info);
  * random.seed(seed + env_offset + e) (CPython MT19937; mvmnt.py:47-79 draw order:
  * targets (angle, dist) then agents (x, y, angle)). Resets time, contacts, status.
  * Writes the initial observation (Flock.obs, mvmnt.py:79) into `out` if non-NULL.
+ * Every env's seed is taken modulo 2^64 as a key of one or two 32-bit words, which is random.seed's
+ * meaning only for seed + env_offset + e in [0, 2^64): CPython seeds a negative int by its absolute
+ * value and an int of 2^64 or more by a longer key. The caller keeps seed >= 0 and the envs' seeds in
+ * that range (macm_tdm_reset too); the Python handles raise ValueError outside it.
  */
 int macm_world_reset(macm_world* w, uint64_t seed, int64_t env_offset, const macm_outputs* out,
                      void* stream);
