@@ -10,9 +10,9 @@ coordinates small), exact distance ties on an integer lattice, fat AABBs far wid
 others, and long dense rollouts of the C3 / C5 shapes."""
 import numpy as np
 import pytest
-import torch
 
 import test_gpu_parity
+from constructed import inject
 from test_gpu_parity import check_rollout, rand_actions
 
 pytestmark = pytest.mark.gpu
@@ -25,41 +25,6 @@ def make_pair(*a, **kw):
     vec, orc = test_gpu_parity.make_pair(*a, **kw)
     vec.world.set_debug(_abi.DEBUG_SWEEP_CELLS)
     return vec, orc
-
-
-def inject(vec, orc, pos, fat_fn=None):
-    """Place bodies at pos [E, N, 2] (zero velocity, fresh fat AABBs — or fat_fn(e, fat) — and
-    the pair list of the overlapping fat AABBs in FindNewContacts order) in both worlds."""
-    E, N = pos.shape[:2]
-    C = vec.world.C
-    # one step first: the oracle's first Step runs the pending FindNewContacts of the freshly
-    # created fixtures (Box2D's e_newFixture), which would rebuild the injected fat AABBs
-    idle = np.ones((E, N, 3), np.uint8)
-    orc.step(idle)
-    vec.step(torch.from_numpy(idle).cuda())
-    st = orc.get_state(C)
-    for e in range(E):
-        p = pos[e].astype(np.float32)
-        st["pos"][e] = p
-        st["vel"][e] = 0.0
-        st["sleep"][e] = 0.0
-        st["fat"][e] = np.concatenate([(p - np.float32(0.5)) - np.float32(0.1),
-                                       (p + np.float32(0.5)) + np.float32(0.1)], -1)
-        if fat_fn is not None:
-            fat_fn(e, st["fat"][e])
-        f = st["fat"][e]
-        lo, hi = f[:, :2], f[:, 2:]
-        ov = ~((lo[None, :, 0] > hi[:, None, 0]) | (lo[None, :, 1] > hi[:, None, 1]) |
-               (lo[:, None, 0] > hi[None, :, 0]) | (lo[:, None, 1] > hi[None, :, 1]))
-        pairs = [(a, b) for a in range(N - 1, -1, -1) for b in np.nonzero(ov[a, a + 1:])[0][::-1] + a + 1]
-        assert len(pairs) <= C
-        st["contact_count"][e] = len(pairs)
-        st["contact_ab"][e] = 0
-        if pairs:
-            st["contact_ab"][e, :len(pairs)] = [a | (int(b) << 16) for a, b in pairs]
-        st["contact_imp"][e] = 0.0
-    orc.set_state(st)
-    vec.set_state(st)
 
 
 def test_sparse_world_neighbours_beyond_the_tile():
