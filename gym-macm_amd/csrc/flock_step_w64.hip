@@ -905,7 +905,7 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
     const void* __restrict__ actions, OT* __restrict__ obs, int32_t* __restrict__ nbr_out,
     float* __restrict__ rew_out, uint8_t* __restrict__ coll_out, uint8_t* __restrict__ done_out,
     const int e = blockIdx.x, const int lane = threadIdx.x, TailObs* tl = nullptr, StepCarry* carry = nullptr,
-    const void* actions_next = nullptr) {
+    const void* actions_next = nullptr, void** pool_out = nullptr) {
   constexpr bool kT = MODE == kTdm;
   static_assert(!CARRY || !kT, "the carried step is Flock's");
 #ifdef MACM_TIMELINE
@@ -938,6 +938,9 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
   };
   __shared__ Pool s_pool;
   static_assert(spill::layout(W, !kT).total <= (int)sizeof(Pool), "the spill step must fit the pool");
+  // the autoreset rollout's in-launch reset works in the pool between two steps (rollout_autoreset.inc)
+  static_assert(sizeof(Pool) >= 4800, "the in-launch reset's LDS (ResetLds) must fit the pool");
+  if (pool_out) *pool_out = &s_pool;
   uint32_t* const s_tab = s_pool.tab;
   float* const s_tln = s_pool.tln;
   float* const s_tlt = s_pool.tlt;
@@ -2302,6 +2305,135 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
 #endif
 }
 
+// Initial proxies (b2DynamicTree::CreateProxy: fat = tight +- 0.1), the first
+// FindNewContacts' list (all overlapping pairs, descending), zeroed dynamics,
+// and the initial observation (Flock.obs, mvmnt.py:79).
+// (The body of flock_init_w64; the autoreset rollout resets an env with it inside the launch.)
+template <typename OT>
+__device__ __forceinline__ void flock_init_env(const StepParams& P, const WorldBuffers& B, int cur,
+                                               OT* __restrict__ obs, int32_t* __restrict__ nbr_out, const int e,
+                                               const int lane) {
+  const int N = P.n_agents;
+  const int C = P.max_contacts;
+  const bool act = lane < N;
+  const size_t ag = (size_t)e * N + lane;
+  float2 p = make_float2(0.0f, 0.0f);
+  float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float ang = 0.0f;
+  float2 tg = make_float2(0.0f, 0.0f);
+  if (act) {
+    p = B.pos[ag];
+    ang = B.angle[ag];
+    tg = B.targets[(size_t)e * P.n_targets + B.tidx[lane]];
+    const float r = P.radius;
+    f = make_float4((p.x - r) - kAabbExtension, (p.y - r) - kAabbExtension, (p.x + r) + kAabbExtension,
+                    (p.y + r) + kAabbExtension);
+    B.fat[ag] = f;
+    B.vel[ag] = make_float2(0.0f, 0.0f);
+    B.sleep[ag] = 0.0f;
+  }
+  unsigned long long m = 0ull;
+  float best = __builtin_inff();
+  int bj = lane == 0 ? 1 : 0;
+  for (int j = 0; j < N; ++j) {
+    const float4 fj = make_float4(bcast(f.x, j), bcast(f.y, j), bcast(f.z, j), bcast(f.w, j));
+    const float dx = bcast(p.x, j) - p.x, dy = bcast(p.y, j) - p.y;
+    const float d2 = dx * dx + dy * dy;
+    if (j > lane && overlap(f, fj)) m |= 1ull << j;
+    if (j != lane && d2 < best) {
+      best = d2;
+      bj = j;
+    }
+  }
+  int total = write_new_pairs(lane, act ? m : 0ull, B.cab[cur] + (size_t)e * C, B.cimp[cur] + (size_t)e * C, C);
+  int st = 0;
+  if (total > C) {
+    st = MACM_ST_CONTACT_OVERFLOW;
+    total = C;
+  }
+  const float bx = __shfl(p.x, bj, W), by = __shfl(p.y, bj, W);
+  if (act) {
+    if (nbr_out) nbr_out[ag] = bj;
+    if (obs) {
+      const int od = P.coord == MACM_COORD_CARTESIAN ? 6 : 4;
+      const float tdx = tg.x - p.x, tdy = tg.y - p.y;
+      write_obs<OT>(obs + ag * od, P.coord, ang, best, bx - p.x, by - p.y, tdx, tdy, tdx * tdx + tdy * tdy);
+    }
+  }
+  if (lane == 0) {
+    B.ccount[cur][e] = total;
+    B.step_count[e] = 0;
+    B.time_passed[e] = 0.0;
+    B.done[e] = 0;
+    B.status[e] = st;
+    if (st) report_status(B, st);
+  }
+}
+
+// TDM world creation (combat.py:78-101): every body active with init_health, zero
+// cooldowns, the fresh listener, initial proxies / pairs as flock_init_w64, and
+// the initial observation (self.obs = self.get_obs(), combat.py:102).
+// (tdm_init_w64's body for the autoreset rollout, as flock_init_env; s_p / s_a: W entries of LDS each.
+// The kernel keeps its own copy below: built from this function its kernarg loads and register
+// allocation changed, and the init kernels' code is to stay what it was. Keep the two in step.)
+template <typename OT>
+__device__ __forceinline__ void tdm_init_env(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
+                                             const TdmBuffers& TB, int cur, OT* __restrict__ obs, const int e,
+                                             const int lane, float2* s_p, float* s_a) {
+  const int N = P.n_agents;
+  const int C = P.max_contacts;
+  const bool act = lane < N;
+  const size_t ag = (size_t)e * N + lane;
+  float2 p = make_float2(0.0f, 0.0f);
+  float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float ang = 0.0f;
+  if (act) {
+    p = B.pos[ag];
+    ang = B.angle[ag];
+    const float r = P.radius;
+    f = make_float4((p.x - r) - kAabbExtension, (p.y - r) - kAabbExtension, (p.x + r) + kAabbExtension,
+                    (p.y + r) + kAabbExtension);
+    B.fat[ag] = f;
+    B.vel[ag] = make_float2(0.0f, 0.0f);
+    B.sleep[ag] = 0.0f;
+    TB.health[ag] = TP.init_health;
+    TB.cd_atk[ag] = 0.0;
+    TB.cd_mov[ag] = 0.0;
+    TB.alive[ag] = 1;
+    if (TB.health_out) TB.health_out[ag] = TP.init_health;
+    if (TB.alive_out) TB.alive_out[ag] = 1;
+  }
+  unsigned long long m = 0ull;
+  for (int j = 0; j < N; ++j) {
+    const float4 fj = make_float4(bcast(f.x, j), bcast(f.y, j), bcast(f.z, j), bcast(f.w, j));
+    if (j > lane && overlap(f, fj)) m |= 1ull << j;
+  }
+  int total = write_new_pairs(lane, act ? m : 0ull, B.cab[cur] + (size_t)e * C, B.cimp[cur] + (size_t)e * C, C);
+  int st = 0;
+  if (total > C) {
+    st = MACM_ST_CONTACT_OVERFLOW;
+    total = C;
+  }
+  s_p[lane] = p;
+  s_a[lane] = ang;
+  const unsigned long long livem = __ballot(act);
+  __syncthreads();
+  const size_t rows = (size_t)e * N * (N - 1);
+  tdm_obs_pairs<OT>(obs ? obs + rows * 4 : nullptr, TB.mask_out ? TB.mask_out + rows : nullptr, N, lane, livem, TP,
+                   s_p, s_a);
+  if (lane == 0) {
+    B.ccount[cur][e] = total;
+    B.step_count[e] = 0;
+    B.time_passed[e] = 0.0;
+    B.done[e] = 0;
+    B.status[e] = st;
+    if (st) report_status(B, st);
+    TB.listener[e] = make_int2(0, -1);
+    TB.winner[e] = -1;
+    if (TB.winner_out) TB.winner_out[e] = -1;
+  }
+}
+
 #ifdef MACM_ROLLOUT_TU
 
 // nsteps consecutive steps of env blockIdx.x in one launch (macm_world_rollout): actions of step k
@@ -2374,6 +2506,9 @@ __device__ __forceinline__ T* traj_row(T* p, size_t k, size_t per_step) {
 constexpr int kRollBalanceMinSteps = 32;
 constexpr int kSchedMaxSize = 4095;
 
+#ifdef MACM_AUTORESET_TU  // flock_rollout_ar_w64.hip: the rollout kernels of worlds with autoreset on
+#include "rollout_autoreset.inc"
+#else
 // order[0..E): the envs by descending contact-list size (ccount, clamped to C); one workgroup.
 // reset2: the workgroup step's handoff counters (Handoff::ctr), zeroed for the step (or NULL)
 __global__ __launch_bounds__(1024) void rollout_sched(const uint32_t* __restrict__ ccount, uint32_t* __restrict__ order,
@@ -2625,6 +2760,7 @@ hipError_t launch_tdm_rollout_w64(const StepParams& P, const WorldBuffers& B, co
   return hipGetLastError();
 }
 
+#endif  // MACM_AUTORESET_TU
 #else  // the one-step kernels, reset / observe kernels and their launchers
 template <int MODE, int NCAP, typename OT, bool SCAL = false>
 __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env_step_w64(
@@ -2634,71 +2770,13 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
   step_w64_body<MODE, NCAP, OT, SCAL>(P, B, TP, TB, cur, actions, obs, nbr_out, rew_out, coll_out, done_out);
 }
 
-// Initial proxies (b2DynamicTree::CreateProxy: fat = tight +- 0.1), the first
-// FindNewContacts' list (all overlapping pairs, descending), zeroed dynamics,
-// and the initial observation (Flock.obs, mvmnt.py:79).
 template <typename OT>
 __global__ __launch_bounds__(W) void flock_init_w64(StepParams P, WorldBuffers B, int cur,
                                                     OT* __restrict__ obs, int32_t* __restrict__ nbr_out,
                                                     const uint8_t* __restrict__ mask) {
   const int e = blockIdx.x;
   if (mask && !mask[e]) return;  // reset_envs: only the masked envs
-  const int lane = threadIdx.x;
-  const int N = P.n_agents;
-  const int C = P.max_contacts;
-  const bool act = lane < N;
-  const size_t ag = (size_t)e * N + lane;
-  float2 p = make_float2(0.0f, 0.0f);
-  float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  float ang = 0.0f;
-  float2 tg = make_float2(0.0f, 0.0f);
-  if (act) {
-    p = B.pos[ag];
-    ang = B.angle[ag];
-    tg = B.targets[(size_t)e * P.n_targets + B.tidx[lane]];
-    const float r = P.radius;
-    f = make_float4((p.x - r) - kAabbExtension, (p.y - r) - kAabbExtension, (p.x + r) + kAabbExtension,
-                    (p.y + r) + kAabbExtension);
-    B.fat[ag] = f;
-    B.vel[ag] = make_float2(0.0f, 0.0f);
-    B.sleep[ag] = 0.0f;
-  }
-  unsigned long long m = 0ull;
-  float best = __builtin_inff();
-  int bj = lane == 0 ? 1 : 0;
-  for (int j = 0; j < N; ++j) {
-    const float4 fj = make_float4(bcast(f.x, j), bcast(f.y, j), bcast(f.z, j), bcast(f.w, j));
-    const float dx = bcast(p.x, j) - p.x, dy = bcast(p.y, j) - p.y;
-    const float d2 = dx * dx + dy * dy;
-    if (j > lane && overlap(f, fj)) m |= 1ull << j;
-    if (j != lane && d2 < best) {
-      best = d2;
-      bj = j;
-    }
-  }
-  int total = write_new_pairs(lane, act ? m : 0ull, B.cab[cur] + (size_t)e * C, B.cimp[cur] + (size_t)e * C, C);
-  int st = 0;
-  if (total > C) {
-    st = MACM_ST_CONTACT_OVERFLOW;
-    total = C;
-  }
-  const float bx = __shfl(p.x, bj, W), by = __shfl(p.y, bj, W);
-  if (act) {
-    if (nbr_out) nbr_out[ag] = bj;
-    if (obs) {
-      const int od = P.coord == MACM_COORD_CARTESIAN ? 6 : 4;
-      const float tdx = tg.x - p.x, tdy = tg.y - p.y;
-      write_obs<OT>(obs + ag * od, P.coord, ang, best, bx - p.x, by - p.y, tdx, tdy, tdx * tdx + tdy * tdy);
-    }
-  }
-  if (lane == 0) {
-    B.ccount[cur][e] = total;
-    B.step_count[e] = 0;
-    B.time_passed[e] = 0.0;
-    B.done[e] = 0;
-    B.status[e] = st;
-    if (st) report_status(B, st);
-  }
+  flock_init_env<OT>(P, B, cur, obs, nbr_out, e, threadIdx.x);
 }
 
 // Observation of the current state (Flock.get_obs) without stepping.
@@ -2737,9 +2815,6 @@ __global__ __launch_bounds__(W) void flock_observe_w64(StepParams P, WorldBuffer
   }
 }
 
-// TDM world creation (combat.py:78-101): every body active with init_health, zero
-// cooldowns, the fresh listener, initial proxies / pairs as flock_init_w64, and
-// the initial observation (self.obs = self.get_obs(), combat.py:102).
 template <typename OT>
 __global__ __launch_bounds__(W) void tdm_init_w64(StepParams P, WorldBuffers B, TdmParams TP, TdmBuffers TB,
                                                   int cur, OT* __restrict__ obs, const uint8_t* __restrict__ mask) {

@@ -41,6 +41,15 @@ hipError_t launch_tdm_rollout_w64(const StepParams& P, const WorldBuffers& B, co
                                   unsigned long long* tail_ctl = nullptr, unsigned tail_tag = 0u, int tail_workers = 0,
                                   int tail_k0 = 0);
 int tdm_rollout_resident_blocks(int n_agents, bool obs_f64);
+// worlds with autoreset on (flock_rollout_ar_w64.hip): the rollout with the in-launch episode reset
+hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
+                                 bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
+                                 int nsteps, unsigned long long astride, int traj, int reload, uint32_t* mt,
+                                 const PoseDraw& D);
+hipError_t launch_tdm_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
+                                     const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
+                                     uint8_t* done, hipStream_t s, int nsteps, unsigned long long astride, int traj,
+                                     uint32_t* mt, const PoseDraw& D);
 hipError_t launch_tdm_init_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                const TdmBuffers& TB, int cur, void* obs, bool obs_f64, const uint8_t* mask,
                                hipStream_t s);
@@ -97,6 +106,7 @@ struct macm_world {
   uint32_t* mt = nullptr;     // [E][kMtStride] per-env MT19937 streams (valid after reset)
   uint8_t* rmask = nullptr;   // [E] reset mask scratch
   bool mt_valid = false;
+  bool autoreset = false;     // macm_world_set_autoreset: step and rollouts restart the envs that end
   uint32_t* hstat = nullptr;  // host-mapped status word (B.host_status is its device alias)
   unsigned long long* bad = nullptr;  // validate_actions: first failing row (device scratch)
   // workgroup-path rollouts: env slices on streams of their own (created on first use)
@@ -123,6 +133,7 @@ struct macm_tdm {
   uint32_t* mt = nullptr;
   uint8_t* rmask = nullptr;
   bool mt_valid = false;
+  bool autoreset = false;  // macm_tdm_set_autoreset
   uint32_t* hstat = nullptr;
   unsigned long long* bad = nullptr;
   int slots_alloc = 0;  // as macm_world
@@ -630,14 +641,9 @@ static int fill_reset_mask(uint8_t* rmask, const uint8_t* env_mask, int E, hipSt
   return MACM_OK;
 }
 
-int macm_world_reset_envs(macm_world* w, const uint8_t* env_mask, const macm_outputs* out, void* stream) {
-  if (!w) return fail(MACM_E_INVALID, "world is NULL");
-  if (!w->mt_valid)
-    return fail(MACM_E_INVALID, "no per-env random streams: the world was placed, not reset (macm_world_reset)");
-  DeviceGuard g(w->device);
-  hipStream_t s = (hipStream_t)stream;
-  int rc = fill_reset_mask(w->rmask, env_mask, w->P.n_envs, s);
-  if (rc) return rc;
+static const char* const kNoStreams = "no per-env random streams: the world was placed, not reset (macm_world_reset)";
+
+static PoseDraw world_pose_draw(const macm_world* w) {
   PoseDraw D;
   memset(&D, 0, sizeof(D));
   D.mode = kFlock;
@@ -645,9 +651,40 @@ int macm_world_reset_envs(macm_world* w, const uint8_t* env_mask, const macm_out
   D.spread = w->cfg.start_spread;
   D.start_x = w->cfg.start_point[0];
   D.start_y = w->cfg.start_point[1];
-  HIP_TRY(launch_draw_poses(w->rmask, w->mt, D, w->P.n_envs, w->B.pos, w->B.angle, s));
+  return D;
+}
+
+// the draw and init launches of the envs masked in w->rmask (the new initial obs / nbr_id into `out`)
+static int world_reset_masked(macm_world* w, const macm_outputs* out, hipStream_t s) {
+  HIP_TRY(launch_draw_poses(w->rmask, w->mt, world_pose_draw(w), w->P.n_envs, w->B.pos, w->B.angle, s));
   HIP_TRY(launch_init(w, out, w->rmask, s));
+  return MACM_OK;
+}
+
+int macm_world_reset_envs(macm_world* w, const uint8_t* env_mask, const macm_outputs* out, void* stream) {
+  if (!w) return fail(MACM_E_INVALID, "world is NULL");
+  if (!w->mt_valid) return fail(MACM_E_INVALID, kNoStreams);
+  DeviceGuard g(w->device);
+  hipStream_t s = (hipStream_t)stream;
+  int rc = fill_reset_mask(w->rmask, env_mask, w->P.n_envs, s);
+  if (rc) return rc;
+  if ((rc = world_reset_masked(w, out, s))) return rc;
   return resync_host_status(w->hstat, w->B.status, w->P.n_envs, s);
+}
+
+int macm_world_set_autoreset(macm_world* w, int32_t on) {
+  if (!w) return fail(MACM_E_INVALID, "world is NULL");
+  w->autoreset = on != 0;
+  return MACM_OK;
+}
+
+// Autoreset after a step's launches (macm_world_step, and every step of a workgroup-path rollout):
+// the step's done flags, as a private copy (the init kernel clears B.done; the output row keeps its
+// 1), mask the draw and init launches. All on the stream, no host round trip; the host-mapped
+// status word is not resynced here.
+static int world_autoreset_step(macm_world* w, const macm_outputs* out, hipStream_t s) {
+  HIP_TRY(hipMemcpyAsync(w->rmask, w->B.done, (size_t)w->P.n_envs, hipMemcpyDeviceToDevice, s));
+  return world_reset_masked(w, out, s);
 }
 
 static int overflow_error(uint32_t st) {
@@ -694,6 +731,7 @@ static HandoffStream* handoff_for(macm_world* w) {
 
 int macm_world_step(macm_world* w, const void* actions, const macm_outputs* out, void* stream) {
   if (!w || !actions || !out || !out->reward) return fail(MACM_E_INVALID, "world/actions/out/reward is NULL");
+  if (w->autoreset && !w->mt_valid) return fail(MACM_E_INVALID, kNoStreams);
   if (const uint32_t st = read_host_status(w->hstat)) return overflow_error(st);
   DeviceGuard g(w->device);
   if (w->cfg.validate_actions) {
@@ -711,6 +749,7 @@ int macm_world_step(macm_world* w, const void* actions, const macm_outputs* out,
     HIP_TRY(launch_step_wg(w->P, w->B, w->cur, w->tcap, actions, out->obs, w->cfg.obs_f64 != 0, out->nbr_id,
                            out->reward, out->collided, out->done, (hipStream_t)stream, handoff_for(w)));
   w->cur ^= 1;
+  if (w->autoreset) return world_autoreset_step(w, out, (hipStream_t)stream);
   return MACM_OK;
 }
 
@@ -774,6 +813,7 @@ static int n_slices() {
 // the env slices a workgroup-path rollout of this world runs (0: none, one stream)
 static int wg_rollout_slices(const macm_world* w) {
   if (w->wave || w->big || w->P.n_envs < kSliceMinEnvs || w->P.n_agents >= kSliceMaxAgents) return 0;
+  if (w->autoreset) return 0;  // the reset launches follow each step's on the one stream (env slices: a follow-up)
   const int S = n_slices();
   return S >= 2 ? S : 0;
 }
@@ -847,6 +887,7 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
   if (!w || !actions || !out || !out->reward) return fail(MACM_E_INVALID, "world/actions/out/reward is NULL");
   if (bots && !out->obs) return fail(MACM_E_INVALID, "out->obs is NULL (the bots act on it)");
   if (bots && w->cfg.action_mode != MACM_ACTION_DISCRETE) return fail(MACM_E_INVALID, "bots.flock acts in discrete mode");
+  if (w->autoreset && !w->mt_valid) return fail(MACM_E_INVALID, kNoStreams);
   if (const uint32_t st = read_host_status(w->hstat)) return overflow_error(st);
   DeviceGuard g(w->device);
   hipStream_t s = (hipStream_t)stream;
@@ -861,8 +902,13 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
       bots ? 0ull
            : (unsigned long long)w->P.n_envs * w->P.n_agents * (mode == 0 ? 3 * sizeof(uint8_t) : 2 * sizeof(float));
   if (w->wave) {  // one launch; astride 0: the closed-loop form of the rollout kernel
-    HIP_TRY(launch_rollout_w64(w->P, w->B, w->cur, actions, out->obs, w->cfg.obs_f64 != 0, out->nbr_id, out->reward,
-                               out->collided, out->done, s, n_steps, astride, traj ? 1 : 0, w->roll_reload));
+    if (w->autoreset)  // the kernels with the in-launch reset
+      HIP_TRY(launch_rollout_ar_w64(w->P, w->B, w->cur, actions, out->obs, w->cfg.obs_f64 != 0, out->nbr_id,
+                                    out->reward, out->collided, out->done, s, n_steps, astride, traj ? 1 : 0,
+                                    w->roll_reload, w->mt, world_pose_draw(w)));
+    else
+      HIP_TRY(launch_rollout_w64(w->P, w->B, w->cur, actions, out->obs, w->cfg.obs_f64 != 0, out->nbr_id, out->reward,
+                                 out->collided, out->done, s, n_steps, astride, traj ? 1 : 0, w->roll_reload));
     if (n_steps & 1) w->cur ^= 1;
     return MACM_OK;
   }
@@ -882,7 +928,13 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
                              ok.collided, ok.done, s, handoff_for(w),
                              bots ? const_cast<unsigned char*>(act_k) + (traj ? rows * 3 : 0) : nullptr));
     w->cur ^= 1;
-    if (bots && w->big)
+    if (w->autoreset) {
+      const int rc = world_autoreset_step(w, &ok, s);
+      if (rc) return rc;
+    }
+    // autoreset: kernel C's fused bot acted on the terminal observation; the bots launch over every
+    // row takes a reset env's next actions from its new initial obs (the other rows: the same actions)
+    if (bots && (w->big || w->autoreset))
       HIP_TRY(launch_bots_flock(ok.obs, w->cfg.obs_f64 != 0, obs_dim(w->cfg), rows,
                                 const_cast<unsigned char*>(act_k) + (traj ? rows * 3 : 0), s));
   }
@@ -1420,14 +1472,9 @@ int macm_tdm_place(macm_tdm* w, const void* pos, const void* angle, const macm_t
   return MACM_OK;
 }
 
-int macm_tdm_reset_envs(macm_tdm* w, const uint8_t* env_mask, const macm_tdm_outputs* out, void* stream) {
-  if (!w) return fail(MACM_E_INVALID, "tdm is NULL");
-  if (!w->mt_valid)
-    return fail(MACM_E_INVALID, "no per-env random streams: the world was placed, not reset (macm_tdm_reset)");
-  DeviceGuard g(w->device);
-  hipStream_t s = (hipStream_t)stream;
-  int rc = fill_reset_mask(w->rmask, env_mask, w->P.n_envs, s);
-  if (rc) return rc;
+static const char* const kNoTdmStreams = "no per-env random streams: the world was placed, not reset (macm_tdm_reset)";
+
+static PoseDraw tdm_pose_draw(const macm_tdm* w) {
   PoseDraw D;
   memset(&D, 0, sizeof(D));
   D.mode = kTdm;
@@ -1435,10 +1482,41 @@ int macm_tdm_reset_envs(macm_tdm* w, const uint8_t* env_mask, const macm_tdm_out
   D.half_width = w->cfg.world_width / 2;
   D.height = w->cfg.world_height;
   D.TP = w->TP;
-  HIP_TRY(launch_draw_poses(w->rmask, w->mt, D, w->P.n_envs, w->B.pos, w->B.angle, s));
+  return D;
+}
+
+int macm_tdm_reset_envs(macm_tdm* w, const uint8_t* env_mask, const macm_tdm_outputs* out, void* stream) {
+  if (!w) return fail(MACM_E_INVALID, "tdm is NULL");
+  if (!w->mt_valid) return fail(MACM_E_INVALID, kNoTdmStreams);
+  DeviceGuard g(w->device);
+  hipStream_t s = (hipStream_t)stream;
+  int rc = fill_reset_mask(w->rmask, env_mask, w->P.n_envs, s);
+  if (rc) return rc;
+  HIP_TRY(launch_draw_poses(w->rmask, w->mt, tdm_pose_draw(w), w->P.n_envs, w->B.pos, w->B.angle, s));
   const TdmBuffers TB = tdm_with_outputs(w, out);
   HIP_TRY(tdm_launch_init(w, TB, out ? out->obs : nullptr, w->rmask, s));
   return resync_host_status(w->hstat, w->B.status, w->P.n_envs, s);
+}
+
+int macm_tdm_set_autoreset(macm_tdm* w, int32_t on) {
+  if (!w) return fail(MACM_E_INVALID, "tdm is NULL");
+  w->autoreset = on != 0;
+  return MACM_OK;
+}
+
+// As world_autoreset_step: the step's done flags (a private copy) mask the draw and init launches.
+// TB / obs: the step's outputs; the init writes the new initial obs and mask there and leaves the
+// terminal health, alive and winner outputs as the step wrote them.
+static int tdm_autoreset_step(macm_tdm* w, const TdmBuffers& TB, void* obs, hipStream_t s) {
+  HIP_TRY(hipMemcpyAsync(w->rmask, w->B.done, (size_t)w->P.n_envs, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(launch_draw_poses(w->rmask, w->mt, tdm_pose_draw(w), w->P.n_envs, w->B.pos, w->B.angle, s));
+  TdmBuffers TBi = TB;
+  TBi.health_out = nullptr;
+  TBi.alive_out = nullptr;
+  TBi.winner_out = nullptr;
+  TBi.snap_out = nullptr;
+  HIP_TRY(tdm_launch_init(w, TBi, obs, w->rmask, s));
+  return MACM_OK;
 }
 
 // The split observation (round 6, tdm_obs_snap.hip). The wave kernel (N <= 64) observes on its one
@@ -1458,7 +1536,7 @@ int macm_tdm_reset_envs(macm_tdm* w, const uint8_t* env_mask, const macm_tdm_out
 static constexpr int kTdmSplitMaxEnvs = 1024, kTdmSplitChunk = 8;
 
 static bool tdm_split_obs(const macm_tdm* w) {
-  if (!w->wave) return false;
+  if (!w->wave || w->autoreset) return false;  // autoreset: the observation inside the step
   const char* v = getenv("MACM_TDM_SPLIT_OBS");
   return v ? atoi(v) != 0 : w->P.n_envs < kTdmSplitMaxEnvs;
 }
@@ -1495,6 +1573,7 @@ static int tdm_split_buffers(macm_tdm* w, size_t rows, hipStream_t s) {
 
 int macm_tdm_step(macm_tdm* w, const void* actions, const macm_tdm_outputs* out, void* stream) {
   if (!w || !actions) return fail(MACM_E_INVALID, "tdm/actions is NULL");
+  if (w->autoreset && !w->mt_valid) return fail(MACM_E_INVALID, kNoTdmStreams);
   if (const uint32_t st = read_host_status(w->hstat)) return overflow_error(st);
   DeviceGuard g(w->device);
   if (w->cfg.validate_actions) {
@@ -1516,6 +1595,7 @@ int macm_tdm_step(macm_tdm* w, const void* actions, const macm_tdm_outputs* out,
   }
   HIP_TRY(tdm_launch_step(w, TB, w->cur, actions, obs, out ? out->done : nullptr, s));
   w->cur ^= 1;
+  if (w->autoreset) return tdm_autoreset_step(w, TB, obs, s);
   return MACM_OK;
 }
 
@@ -1540,6 +1620,7 @@ static int tdm_tail_workers(macm_tdm* w) {
 static constexpr int kTdmTailMaxEnvs = 2048;
 static constexpr int kTdmSnapMinSteps = 32;  // the tail observation's first snapshot allocation, in steps
 static bool tdm_tail_obs(macm_tdm* w) {
+  if (w->autoreset) return false;  // the tail's pose snapshots know nothing of a mid-launch respawn
   const char* v = getenv("MACM_TDM_TAIL_OBS");
   if (v ? atoi(v) == 0 : w->P.n_envs >= kTdmTailMaxEnvs) return false;
   return tdm_tail_workers(w) >= 0;
@@ -1658,6 +1739,7 @@ static int tdm_rollout(macm_tdm* w, const void* actions, int n_steps, const macm
   if (!w || !actions) return fail(MACM_E_INVALID, "tdm/actions is NULL");
   if ((bots || traj) && !out) return fail(MACM_E_INVALID, "out is NULL");
   if (bots && (!out->obs || !out->mask)) return fail(MACM_E_INVALID, "out->obs/mask is NULL (the bots act on them)");
+  if (w->autoreset && !w->mt_valid) return fail(MACM_E_INVALID, kNoTdmStreams);
   if (const uint32_t st = read_host_status(w->hstat)) return overflow_error(st);
   DeviceGuard g(w->device);
   hipStream_t s = (hipStream_t)stream;
@@ -1692,6 +1774,10 @@ static int tdm_rollout(macm_tdm* w, const void* actions, int n_steps, const macm
       const unsigned char* act_k = act + k * kstride;
       HIP_TRY(tdm_launch_step(w, TBk, w->cur, act_k, obs_k, out ? row(out->done, E) : nullptr, s));
       w->cur ^= 1;
+      if (w->autoreset) {  // before the bots: a reset env's next actions come from its new initial obs
+        const int rc = tdm_autoreset_step(w, TBk, obs_k, s);
+        if (rc) return rc;
+      }
       if (bots)
         HIP_TRY(launch_bots_combat(obs_k, TBk.mask_out, w->cfg.obs_f64 != 0, (int)N, (long long)EN,
                                    const_cast<unsigned char*>(act_k) + (traj ? EN * 4 : 0), s));
@@ -1702,8 +1788,13 @@ static int tdm_rollout(macm_tdm* w, const void* actions, int n_steps, const macm
     return tdm_rollout_tail(w, TB, actions, n_steps, out, s, astride);
   if (!bots && out && (out->obs || out->mask) && tdm_split_obs(w))
     return tdm_rollout_split(w, TB, actions, n_steps, out, s, astride, traj);
-  HIP_TRY(launch_tdm_rollout_w64(w->P, w->B, w->TP, TB, w->cur, actions, out ? out->obs : nullptr,
-                                 w->cfg.obs_f64 != 0, out ? out->done : nullptr, s, n_steps, astride, traj ? 1 : 0));
+  if (w->autoreset)  // the kernels with the in-launch reset (the observation inside the step)
+    HIP_TRY(launch_tdm_rollout_ar_w64(w->P, w->B, w->TP, TB, w->cur, actions, out ? out->obs : nullptr,
+                                      w->cfg.obs_f64 != 0, out ? out->done : nullptr, s, n_steps, astride, traj ? 1 : 0,
+                                      w->mt, tdm_pose_draw(w)));
+  else
+    HIP_TRY(launch_tdm_rollout_w64(w->P, w->B, w->TP, TB, w->cur, actions, out ? out->obs : nullptr,
+                                   w->cfg.obs_f64 != 0, out ? out->done : nullptr, s, n_steps, astride, traj ? 1 : 0));
   if (n_steps & 1) w->cur ^= 1;
   return MACM_OK;
 }

@@ -1,0 +1,308 @@
+// rollout_autoreset.inc — the multi-step wave kernels of a world with autoreset on
+// (macm_world_set_autoreset / macm_tdm_set_autoreset): env_rollout_w64's loop with the episode
+// restart inside it. Included by flock_step_w64.hip in the translation unit flock_rollout_ar_w64.hip
+// only, so the kernels of worlds without autoreset stay the objects they were.
+//
+// An env whose step k sets `done` is reset by its own wave before step k + 1, exactly as
+// macm_*_reset_envs would with that step's done flags as the mask:
+//   draw_poses_wave : the env's CPython MT19937 stream (env_reset.hip: [E][kMtStride] words in HBM)
+//                     continued by one wave: state into LDS, one twist at most (6 N <= 384 words a
+//                     reset), 6 N tempered words, random() = res53 and the pose formulas of
+//                     draw_poses_kernel in the same exactly rounded double arithmetic, state back;
+//   *_init_env      : the bodies of the init kernels (flock_init_w64 / tdm_init_w64): zero dynamics,
+//                     fresh fat AABBs, the first FindNewContacts list into the buffer the next step
+//                     reads, the bookkeeping cleared, and the new episode's initial observation
+//                     into step k's output row (obs, nbr_id / mask). The terminal values of step k
+//                     (done, reward, collided; TDM winner, health, alive) stay as the step wrote them.
+// Every LDS array of the step is dead between two steps: the MT state, the drawn words and TDM
+// init's pose arrays (ResetLds) lie over the step's contact pool, so the kernels' LDS is the
+// step's. After a reset the next step loads from global memory behind the workgroup fence (the
+// carried Flock step: StepCarry::valid = false, which discards the carried next-step actions too).
+
+constexpr int kMtN = 624, kMtM = 397;
+
+__device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
+  y ^= (y >> 11);
+  y ^= (y << 7) & 0x9d2c5680u;
+  y ^= (y << 15) & 0xefc60000u;
+  y ^= (y >> 18);
+  return y;
+}
+
+__device__ __forceinline__ uint32_t mt_mix(uint32_t hi, uint32_t lo, uint32_t src) {
+  const uint32_t y = (hi & 0x80000000u) | (lo & 0x7fffffffu);
+  return src ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+}
+
+struct ResetLds {
+  uint32_t mt[kMtN];  // 2,496 B
+  uint32_t w[6 * W];  // 1,536 B: three random() of two words per agent
+  float2 p[W];        // TDM init's poses (tdm_init_env)
+  float a[W];
+};
+
+// One MT19937 twist of s_mt in place by one wave: the four phases of mt_twist (env_reset.hip), each
+// reading only values final for it, with the wave's in-order LDS accesses in place of the block
+// barrier (wave_lds_sync). ceil(227 / 64) = 4 values per lane and phase.
+__device__ __forceinline__ void mt_twist_wave(uint32_t* s_mt, int lane) {
+  const int lo[4] = {0, kMtN - kMtM, 2 * (kMtN - kMtM), kMtN - 1};
+  const int hi[4] = {kMtN - kMtM, 2 * (kMtN - kMtM), kMtN - 1, kMtN};
+  for (int ph = 0; ph < 4; ++ph) {
+    uint32_t v[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      const int k = lo[ph] + lane + n * W;
+      v[n] = 0u;
+      if (k < hi[ph]) {
+        const int src = k + kMtM < kMtN ? k + kMtM : k + kMtM - kMtN;
+        v[n] = mt_mix(s_mt[k], s_mt[k + 1 < kMtN ? k + 1 : 0], s_mt[src]);
+      }
+    }
+    wave_lds_sync();
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      const int k = lo[ph] + lane + n * W;
+      if (k < hi[ph]) s_mt[k] = v[n];
+    }
+    wave_lds_sync();
+  }
+}
+
+// The next 3 N random() of env stream g as the poses of the env's N <= 64 agents (lane = agent),
+// stored to pos / angle rows ag; the stream's state and position go back to g.
+template <int MODE>
+__device__ __forceinline__ void draw_poses_wave(uint32_t* __restrict__ g, const PoseDraw& D, ResetLds* L, int N,
+                                                int lane, size_t ag, float2* __restrict__ pos,
+                                                float* __restrict__ angle) {
+  for (int k = lane; k < kMtN; k += W) L->mt[k] = g[k];
+  int idx = __builtin_amdgcn_readfirstlane((int)g[kMtN]);
+  wave_lds_sync();
+  const int need = 6 * N;
+  for (int got = 0; got < need;) {
+    if (idx >= kMtN) {
+      mt_twist_wave(L->mt, lane);
+      idx = 0;
+    }
+    const int take = min(kMtN - idx, need - got);
+    for (int w = lane; w < take; w += W) L->w[got + w] = mt_temper(L->mt[idx + w]);
+    got += take;
+    idx += take;
+    wave_lds_sync();
+  }
+  if (lane < N) {
+    double r[3];
+    for (int q = 0; q < 3; ++q) {  // random.random(): genrand_res53
+      const uint32_t a = L->w[6 * lane + 2 * q] >> 5, b = L->w[6 * lane + 2 * q + 1] >> 6;
+      r[q] = (a * 67108864.0 + b) * (1.0 / 9007199254740992.0);
+    }
+    double x, y;
+    if constexpr (MODE == kFlock) {  // mvmnt.py:62-63
+      x = D.spread * (r[0] - 0.5) + D.start_x;
+      y = D.spread * (r[1] - 0.5) + D.start_y;
+    } else {  // combat.py:83-84
+      x = r[0] * ((double)tdm_team_of(D.TP, lane) + D.half_width);
+      y = r[1] * D.height;
+    }
+    const double a = (-1.0 + (1.0 - -1.0) * r[2]) * M_PI;  // random.uniform(-1, 1) * np.pi
+    pos[ag] = make_float2((float)x, (float)y);
+    angle[ag] = (float)a;
+  }
+  for (int k = lane; k < kMtN; k += W) g[k] = L->mt[k];
+  if (lane == 0) g[kMtN] = (uint32_t)idx;
+}
+
+// macm_*_reset_envs of env e by its own wave between two steps of a rollout. `cur` is the list
+// buffer the next step reads; obs / nbr_out / TB.mask_out are step k's output rows. The init body
+// reads the poses back from the rows this lane just stored (a lane's accesses to one address stay
+// in order). TDM: the terminal health / alive / winner outputs are kept (the init kernel would
+// overwrite them).
+template <int MODE, typename OT>
+__device__ __forceinline__ void reset_env_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
+                                              TdmBuffers TB, const PoseDraw& D, uint32_t* __restrict__ mt, int cur,
+                                              OT* __restrict__ obs, int32_t* __restrict__ nbr_out, int e, int lane,
+                                              void* lds) {
+  ResetLds* const L = static_cast<ResetLds*>(lds);
+  const size_t ag = (size_t)e * P.n_agents + lane;
+  draw_poses_wave<MODE>(mt + (size_t)e * kMtStride, D, L, P.n_agents, lane, ag, B.pos, B.angle);
+  if constexpr (MODE == kTdm) {
+    TB.health_out = nullptr;
+    TB.alive_out = nullptr;
+    TB.winner_out = nullptr;
+    tdm_init_env<OT>(P, B, TP, TB, cur, obs, e, lane, L->p, L->a);
+  } else {
+    flock_init_env<OT>(P, B, cur, obs, nbr_out, e, lane);
+  }
+}
+
+template <typename OT>
+struct RolloutArArgs {  // the kernel's only argument (kernarg offset 0)
+  RolloutArgs<OT> A;
+  uint32_t* mt;  // [E][kMtStride] the envs' streams
+  PoseDraw D;
+};
+
+// env_rollout_w64 with the in-launch reset; no tail or split observation (their pose snapshots know
+// nothing of a mid-launch respawn: TDM observes inside the step).
+template <int MODE, int NCAP, typename OT, bool SCAL = false, bool CARRY = false>
+__global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env_rollout_ar_w64(RolloutArArgs<OT> R0) {
+  const int nsteps = R0.A.nsteps;
+  const bool bal = R0.A.B.sched && nsteps >= kRollBalanceMinSteps;  // as in launch_roll_ar
+  const int env = bal ? (int)R0.A.B.sched[R0.A.sched_off + blockIdx.x] : (int)blockIdx.x;
+  StepCarry cy{};  // CARRY; not valid: the first step loads
+  for (int k = 0; k < nsteps; ++k) {
+    // as env_rollout_w64: the arguments afresh every step, through a pointer the compiler cannot see through
+    const __attribute__((address_space(4))) RolloutArArgs<OT>* ka =
+        (const __attribute__((address_space(4))) RolloutArArgs<OT>*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    const RolloutArArgs<OT>& R = *(const RolloutArArgs<OT>*)ka;
+    const RolloutArgs<OT>& A = R.A;
+    const int N = A.P.n_agents, lane = threadIdx.x;
+    const size_t EN = (size_t)A.P.n_envs * N;
+    const size_t kr = A.traj ? (size_t)k : 0;  // output row of this step
+    const size_t od = MODE == kTdm ? (size_t)(N - 1) * 4 : (A.P.coord == MACM_COORD_CARTESIAN ? 6 : 4);
+    OT* const obs = traj_row(A.obs, kr, EN * od);
+    int32_t* const nbr = traj_row(A.nbr_out, kr, EN);
+    TdmBuffers TB = A.TB;
+    if constexpr (MODE == kTdm) {
+      TB.mask_out = traj_row(TB.mask_out, kr, EN * (N - 1));
+      TB.health_out = traj_row(TB.health_out, kr, EN);
+      TB.alive_out = traj_row(TB.alive_out, kr, EN);
+      TB.winner_out = traj_row(TB.winner_out, kr, (size_t)A.P.n_envs);
+    }
+    const size_t abytes = MODE == kTdm ? 4 : 3;  // closed loop: uint8 actions per agent
+    uint8_t* const pol_in = A.policy_act ? A.policy_act + kr * EN * abytes : nullptr;
+    __builtin_amdgcn_s_setprio(0);  // as at a launch: the chain raises it again
+    int sl = (int)threadIdx.x;
+    if constexpr (MODE == kTdm) asm volatile("" : "+v"(sl));
+    void* lds = nullptr;  // the step's contact pool, dead once the step ends
+    if constexpr (CARRY) {
+      const unsigned char* const act_k = static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride;
+      step_w64_body<MODE, NCAP, OT, SCAL, true>(A.P, A.B, A.TP, TB, (A.cur ^ k) & 1, act_k, obs, nbr,
+                                                traj_row(A.rew_out, kr, EN), traj_row(A.coll_out, kr, EN),
+                                                traj_row(A.done_out, kr, (size_t)A.P.n_envs), env, sl, nullptr, &cy,
+                                                k + 1 < nsteps ? act_k + A.astride : nullptr, &lds);
+    } else {
+      step_w64_body<MODE, NCAP, OT, SCAL>(A.P, A.B, A.TP, TB, A.cur ^ (k & 1),
+                                          pol_in ? pol_in : static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride,
+                                          obs, nbr, traj_row(A.rew_out, kr, EN), traj_row(A.coll_out, kr, EN),
+                                          traj_row(A.done_out, kr, (size_t)A.P.n_envs), env, sl, nullptr, nullptr, nullptr,
+                                          &lds);
+    }
+    // the step's done flag, wave-uniform once broadcast from lane 0, which stored it (a lane's
+    // accesses to one address stay in order)
+    // (TDM: the lane index opaque once more, or what the reset derives from it is computed before
+    // the step and held across it: 5 VGPRs in scratch)
+    int rl = (int)threadIdx.x;
+    if constexpr (MODE == kTdm) asm volatile("" : "+v"(rl));
+    int dn = 0;
+    if (rl == 0) dn = A.B.done[env];
+    dn = __builtin_amdgcn_readfirstlane(dn);
+    if constexpr (CARRY) {
+      if (dn || (A.cur & kRollReloadBit)) cy.valid = false;
+      if (!cy.valid) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    } else {
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    }
+    __syncthreads();
+    if (dn) {
+      // behind the fence: the reset's stores follow the step's to the same rows (state, list, obs)
+      reset_env_w64<MODE, OT>(A.P, A.B, A.TP, TB, R.D, R.mt, (A.cur ^ (k + 1)) & 1, obs, nbr, env, rl, lds);
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      __syncthreads();
+    }
+    if constexpr (!CARRY) {
+      if (pol_in) {  // every agent row, as the bots kernel over all E x N rows; a reset env: its new initial obs
+        uint8_t* const pol_out = A.traj ? pol_in + EN * abytes : pol_in;
+        if (lane < N) {
+          const size_t row = (size_t)env * N + lane;
+          if constexpr (MODE == kTdm)
+            bot_combat_row(obs + row * (N - 1) * 4, TB.mask_out + row * (N - 1), N, pol_out + row * 4);
+          else
+            bot_flock_row(obs + row * od, (int)od, pol_out + row * 3);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __syncthreads();
+      }
+    }
+  }
+}
+
+hipError_t launch_env_order(const uint32_t* ccount, uint32_t* order, int E, int C, hipStream_t s, unsigned int* reset2);
+
+template <int MODE, int NCAP, typename OT, bool SCAL = false>
+static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hipStream_t s, const StepParams& P,
+                           const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur, const void* actions,
+                           void* obs, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, int reload, uint32_t* mt,
+                           const PoseDraw& D) {
+  // astride == 0: closed loop, `actions` is the bots' action buffer
+  uint8_t* pol = astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(actions)) : nullptr;
+  if (B.sched && nsteps >= kRollBalanceMinSteps) {  // the balanced env order, as launch_roll
+    if (launch_env_order(reinterpret_cast<const uint32_t*>(B.ccount[cur]), B.sched, P.n_envs, P.max_contacts, s, nullptr) !=
+        hipSuccess)
+      return;  // no rollout on a stale order (the caller reports it)
+  }
+  RolloutArArgs<OT> R{{P, B, TP, TB, actions, (OT*)obs, nbr, rew, coll, done, astride, cur, nsteps, pol, traj, 0, nullptr,
+                       0u, 0},
+                      mt,
+                      D};
+  if constexpr (MODE == kFlock) {
+    if (!pol) {  // actions given: the carried step
+      if (reload) R.A.cur |= kRollReloadBit;
+      hipLaunchKernelGGL((env_rollout_ar_w64<MODE, NCAP, OT, SCAL, true>), dim3(P.n_envs), dim3(W), 0, s, R);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((env_rollout_ar_w64<MODE, NCAP, OT, SCAL>), dim3(P.n_envs), dim3(W), 0, s, R);
+}
+
+// the same instantiation choice as launch_rollout_w64 / launch_tdm_rollout_w64
+hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
+                                 bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
+                                 int nsteps, unsigned long long astride, int traj, int reload, uint32_t* mt,
+                                 const PoseDraw& D) {
+  const TdmParams TP{};
+  const TdmBuffers TB{};
+  const bool small = P.n_agents <= 32;
+  if (obs_f64) {
+    if (small)
+      launch_roll_ar<kFlock, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
+                                        reload, mt, D);
+    else
+      launch_roll_ar<kFlock, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
+                                        reload, mt, D);
+  } else {
+    if (small)
+      launch_roll_ar<kFlock, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
+                                       reload, mt, D);
+    else if (P.n_envs >= kScalarSweepMinEnvs)
+      launch_roll_ar<kFlock, 64, float, true>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll,
+                                             done, reload, mt, D);
+    else
+      launch_roll_ar<kFlock, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
+                                       reload, mt, D);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_tdm_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
+                                     const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
+                                     uint8_t* done, hipStream_t s, int nsteps, unsigned long long astride, int traj,
+                                     uint32_t* mt, const PoseDraw& D) {
+  const bool small = P.n_agents <= 32;
+  if (obs_f64) {
+    if (small)
+      launch_roll_ar<kTdm, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
+                                      nullptr, done, 0, mt, D);
+    else
+      launch_roll_ar<kTdm, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
+                                      nullptr, done, 0, mt, D);
+  } else {
+    if (small)
+      launch_roll_ar<kTdm, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
+                                     nullptr, done, 0, mt, D);
+    else
+      launch_roll_ar<kTdm, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
+                                     nullptr, done, 0, mt, D);
+  }
+  return hipGetLastError();
+}

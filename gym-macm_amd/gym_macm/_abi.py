@@ -200,6 +200,7 @@ SIGNATURES = {
     "macm_world_reset": (c_int, [c_void_p, c_uint64, c_int64, POINTER(MacmOutputs), c_void_p]),
     "macm_world_place": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(MacmOutputs), c_void_p]),
     "macm_world_reset_envs": (c_int, [c_void_p, c_void_p, POINTER(MacmOutputs), c_void_p]),
+    "macm_world_set_autoreset": (c_int, [c_void_p, c_int32]),
     "macm_world_step": (c_int, [c_void_p, c_void_p, POINTER(MacmOutputs), c_void_p]),
     "macm_world_rollout": (c_int, [c_void_p, c_void_p, c_int, POINTER(MacmOutputs), c_void_p]),
     "macm_world_rollout_bots": (c_int, [c_void_p, c_void_p, c_int, POINTER(MacmOutputs), c_void_p]),
@@ -220,6 +221,7 @@ SIGNATURES = {
     "macm_tdm_reset": (c_int, [c_void_p, c_uint64, c_int64, POINTER(MacmTdmOutputs), c_void_p]),
     "macm_tdm_place": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(MacmTdmOutputs), c_void_p]),
     "macm_tdm_reset_envs": (c_int, [c_void_p, c_void_p, POINTER(MacmTdmOutputs), c_void_p]),
+    "macm_tdm_set_autoreset": (c_int, [c_void_p, c_int32]),
     "macm_tdm_step": (c_int, [c_void_p, c_void_p, POINTER(MacmTdmOutputs), c_void_p]),
     "macm_tdm_rollout": (c_int, [c_void_p, c_void_p, c_int, POINTER(MacmTdmOutputs), c_void_p]),
     "macm_tdm_rollout_bots": (c_int, [c_void_p, c_void_p, c_int, POINTER(MacmTdmOutputs), c_void_p]),

@@ -44,7 +44,8 @@ class TdmWorld:
     """E independent TDM envs of one configuration on one GPU. Output tensors are
     owned by this object and overwritten by every call."""
 
-    def __init__(self, cfg: _abi.MacmTdmConfig, n_envs: int = 1, device=None, host_outputs: bool = False):
+    def __init__(self, cfg: _abi.MacmTdmConfig, n_envs: int = 1, device=None, host_outputs: bool = False,
+                 autoreset: bool = False):
         self.L = _abi.lib()
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
@@ -80,6 +81,16 @@ class TdmWorld:
         for t in range(cfg.n_teams):
             team += [t] * cfg.team_size[t]
         self.team = np.array(team, np.int32)
+        if autoreset:
+            self.set_autoreset(True)
+
+    def set_autoreset(self, on: bool = True) -> None:
+        """Autoreset (macm_tdm_set_autoreset; off at creation): an env that ends (a team wiped out, or
+        the time limit) starts its next episode before its next step, as reset_envs(done) would, in
+        step() and inside every rollout launch. The outputs of such a step keep the terminal done,
+        winner, health and alive; obs and mask of the reset envs are the new episode's. Needs the
+        device streams of reset(): a placed world raises MacmError from step() and the rollouts."""
+        _abi.check(self.L.macm_tdm_set_autoreset(self.h, 1 if on else 0), "macm_tdm_set_autoreset")
 
     def __del__(self):
         h = getattr(self, "h", None)

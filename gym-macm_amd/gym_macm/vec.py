@@ -43,6 +43,8 @@ class FlockVec(object):
         self.seed = int(seed)
         self.env_offset = int(env_offset)
         self.autoreset = bool(autoreset)
+        if self.autoreset:
+            self.world.set_autoreset(True)
         self.obs, self.nbr_id = self.world.reset(self.seed, self.env_offset)
 
     @property
@@ -67,19 +69,16 @@ class FlockVec(object):
         synchronisation may be a few queued steps later (check_status() is exact) —
         MacmInvalidActionError with ``validate_actions=True`` and an
         action outside the action space (no env is stepped, as the reference asserts first)."""
-        out = self.world.step(actions)
-        if self.autoreset:
-            self.world.reset_envs(self.world.done)
-        return out
+        return self.world.step(actions)
 
     def rollout(self, actions, trajectory=False, traj=None):
         """K steps of every env with actions given in advance ([K, E, N, 3] on the device, e.g. a
         random-action rollout), one launch (World.rollout): each env runs its K steps back to back.
-        Same results as K step() calls without autoreset; returns the last step's outputs, or with
+        Same results as K step() calls; returns the last step's outputs, or with
         ``trajectory=True`` every step's (World.rollout_traj: a dict of [K, ...] tensors, written
-        into ``traj`` if given). With ``autoreset`` a step-by-step loop is required."""
-        if self.autoreset:
-            raise ValueError("rollout steps without autoreset; use step() with autoreset=True")
+        into ``traj`` if given). With ``autoreset`` an env whose episode ends at step k restarts
+        inside the launch before step k + 1 (World.set_autoreset): row k keeps the terminal done,
+        reward and collided, and its obs / nbr_id hold the new episode's initial observation."""
         if trajectory:
             return self.world.rollout_traj(actions, traj)
         return self.world.rollout(actions)
@@ -88,9 +87,9 @@ class FlockVec(object):
         """n_steps of the closed loop step -> bots.flock -> step in one launch (World.rollout_bots);
         ``actions`` (uint8 [E, N, 3]) holds the first step's actions on entry, the next on return.
         ``trajectory=True``: actions is [n_steps + 1, E, N, 3] and every step's outputs and actions
-        are kept (World.rollout_bots_traj)."""
-        if self.autoreset:
-            raise ValueError("rollout_bots steps without autoreset; use step() with autoreset=True")
+        are kept (World.rollout_bots_traj). With ``autoreset`` the envs that end restart inside the
+        launch, and the bot's next action of such an env is taken from its new initial observation,
+        as in the loop step -> reset_envs(done) -> bots."""
         if trajectory:
             return self.world.rollout_bots_traj(actions, n_steps, traj)
         return self.world.rollout_bots(actions, n_steps)

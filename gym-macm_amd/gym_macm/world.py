@@ -159,6 +159,14 @@ class World:
                    "macm_world_reset_envs")
         return self.obs, self.nbr_id
 
+    def set_autoreset(self, on: bool = True) -> None:
+        """Autoreset (macm_world_set_autoreset; off at creation): an env whose step sets done starts
+        its next episode before its next step, as reset_envs(done) would, in step() and inside every
+        rollout launch. The outputs of such a step keep the terminal done / reward / collided; obs and
+        nbr_id of the reset envs are the new episode's initial observation. Needs the device streams
+        of reset(): a placed world raises MacmError from step() and the rollouts."""
+        _abi.check(self.L.macm_world_set_autoreset(self.h, 1 if on else 0), "macm_world_set_autoreset")
+
     # -- hot path ------------------------------------------------------------
     def step(self, actions: torch.Tensor):
         """actions: discrete uint8/int8 [E,N,3] or continuous float32 [E,N,2], on this device."""

@@ -359,6 +359,26 @@ int macm_world_place(macm_world* w, const void* pos, const void* angle, const vo
 int macm_world_reset_envs(macm_world* w, const uint8_t* env_mask, const macm_outputs* out, void* stream);
 
 /*
+ * Autoreset (off at creation; on != 0 turns it on). With it on, an env whose step sets `done` starts
+ * its next episode before its next step, exactly as macm_world_reset_envs would with that step's
+ * done flags as the mask (the env's stream continued, targets kept), in macm_world_step and inside
+ * every rollout: on the wave path (N <= 64) the env's own wave resets it within the launch, on the
+ * workgroup path the draw and init launches follow each step's on the same stream (such rollouts
+ * run without env slices: macm_world_info.rollout_slices is 0). The usual vector-env convention
+ * holds for the outputs of such a step (row k of a trajectory): done (1), reward and collided are
+ * the terminal values as the step wrote them; obs and nbr_id of the reset envs are the new
+ * episode's initial observation (NULL fields stay unwritten), and the closed loop's next action of
+ * a reset env is taken from it. Counters, reward sums and spilled are those of the loop
+ * step -> reset_envs(done) [-> bots]. A reset env's device status word is rewritten as by
+ * reset_envs; the host-mapped status word (what makes a step return MACM_E_OVERFLOW) stays set
+ * until the next macm_world_reset / reset_envs / place / set_state: a reset inside a launch cannot
+ * resync it. With autoreset on and no device streams (the world was placed, not reset) step and
+ * every rollout return MACM_E_INVALID with reset_envs' message and launch nothing. A NULL world gives
+ * MACM_E_INVALID. Additive: no struct changed, MACM_ABI_VERSION stays 9.
+ */
+int macm_world_set_autoreset(macm_world* w, int32_t on);
+
+/*
  * One env.step for all E envs.
  *   actions: device pointer. Discrete: uint8/int8 [E, N, 3] in {0,1,2}
  *   (MultiDiscrete([3,3,3]), mvmnt.py:143-145). Continuous: float32 [E, N, 2] in [-1,1].
@@ -487,6 +507,17 @@ int macm_tdm_place(macm_tdm* w, const void* pos, const void* angle, const macm_t
  * init_health, zero cooldowns, a fresh listener, winner -1.
  */
 int macm_tdm_reset_envs(macm_tdm* w, const uint8_t* env_mask, const macm_tdm_outputs* out, void* stream);
+
+/*
+ * As macm_world_set_autoreset for TDM: an env that ends (a team wiped out, or the time limit) is
+ * reset as by macm_tdm_reset_envs before its next step, in macm_tdm_step and inside every rollout.
+ * The outputs of such a step keep the terminal done (1), winner, health and alive as the step
+ * wrote them (the trajectory shows who won); obs and mask of the reset envs are the new episode's.
+ * Rollouts of such a world observe inside the step: macm_tdm_launch_flags reports 0 and
+ * macm_tdm_reserve is a no-op. Status, placed worlds and NULL as for macm_world_set_autoreset.
+ * Additive: no struct changed, MACM_ABI_VERSION stays 9.
+ */
+int macm_tdm_set_autoreset(macm_tdm* w, int32_t on);
 
 /*
  * One TDM.step for all E envs (combat.py:104-184). actions: device uint8

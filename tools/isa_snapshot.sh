@@ -10,7 +10,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vec
 for f in csrc/*.hip; do
   b=$(basename "$f" .hip)
   extra=""
-  [ "$b" = flock_rollout_w64 ] && extra="-mllvm -disable-machine-licm"
+  { [ "$b" = flock_rollout_w64 ] || [ "$b" = flock_rollout_ar_w64 ]; } && extra="-mllvm -disable-machine-licm"
   /opt/rocm/bin/hipcc $FLAGS $extra --cuda-device-only -S -o "$OUT/$b.s" "$f" &
 done
 wait
