@@ -702,6 +702,110 @@ __device__ __forceinline__ void near2_step(const float4* s_pc2, float4* win, fve
   if constexpr (K + 1 < 16) near2_step<K + 1, SCAL>(s_pc2, win, cme, st);
 }
 
+// ---- nearest neighbour from per-agent candidate lists (Flock wave rollouts, NCAP = 64) -----------
+// Agents move ~0.01 m a step and their nearest neighbours are ~1 m away, so a rollout's wave keeps,
+// between the steps of one launch, per agent i the set S_i of agents that can be its nearest and the
+// position c0_i at which S_i was built; a list step scans S_i instead of all 64 records.
+//
+// Notation: u = 2^-24; D(i,j) the real distance of the (exact) float32 positions; fl_d2(i,j) the
+// sweep's value, dx = fl(xj - xi), dy likewise, fl(fl(dx dx) + fl(dy dy)): four roundings on any path
+// from a difference to the sum, all terms >= 0, so
+//     fl_d2 = D^2 (1 + t),  |t| <= eta := (1 + u)^4 - 1 < 4.01 u                                 (R)
+// (underflow: a product below 2^-126 has an absolute error far below the pad of (B) squared).
+//
+// (B) Build at positions c0: best_i = min_j fl_d2_0(i,j) (the plain sweep), then
+//     S_i = { j != i : fl_d2_0(i,j) <= thr2_i },  thr2_i = fl(fl(t t) (1 + 2^-18)),  t = fl(fl(sqrt(best_i)) + s).
+//     With n in S_i the build's nearest and by (R), every j outside S_i has
+//         D0(i,j) > (D0(i,n) + s)(1 + 2 eta):
+//     thr2_i >= (D0_n + s)^2 (1 + 2 eta)^2 (1 + eta) is needed, and D0_n <= sqrt(best_i / (1 - eta)).
+//     The factor required on the computed t t is (1 + 2 eta)^2 (1 + eta) / (1 - eta) < 1 + 25 u, the
+//     roundings of sqrt (v_sqrt_f32: 1 ulp), of the sum, of t t and of the last product lose at most
+//     (1 + 2 u)^2 (1 + u)^2 (1 + u)^2 < 1 + 9 u; 1 + 2^-18 = 1 + 64 u covers both with room.
+// (V) Valid while every agent's real displacement |c_i - c0_i| <= s / 4. The test is on
+//     fl(dx dx + dy dy) <= kNearMove2 = (s / 4)^2 (1 - 2^-20), which by (R) implies it (4.01 u < 16 u);
+//     a NaN fails the `<=` and rebuilds.
+// (C) While valid, for j outside S_i (triangle inequality, each distance changes by at most 2 (s / 4)):
+//         D(i,j) >= D0(i,j) - s/2 > D0_n + s/2 + 2 eta (D0_n + s) >= D(i,n) + 2 eta D(i,n),
+//     hence D_j^2 (1 - eta) > D_n^2 (1 + eta) and fl_d2(i,j) > fl_d2(i,n) >= min over S_i: no agent
+//     outside S_i is the nearest or ties with it. The list step scans S_i in ascending j with strict
+//     '<' on the same fl_d2, which is then the plain sweep's result, value and index.
+// Every margin errs towards a larger list or an earlier rebuild. An env in which some list exceeds
+// kNearCap (a dense start, a converged flock) takes the plain sweep for kNearRetry steps before it
+// tries again, and for twice as many after every further failure in a row, up to kNearRetryMax: a
+// failed rebuild costs about a plain sweep on top of the step's own. s and the cap: the CPU model
+// (tests/near_candidates_ref.py) over oracle traces, re-swept on the device.
+constexpr float kNearS = 1.0f;
+constexpr int kNearCap = 12;
+constexpr int kNearRetry = 8, kNearRetryMax = 64;
+constexpr float kNearPad = 1.0f + 0x1p-18f;
+constexpr float kNearMove2 = (kNearS * 0.25f) * (kNearS * 0.25f) * (1.0f - 0x1p-20f);
+// the wave-uniform list state (s_nl_state): none, valid, or dense with 1 + (steps until the retry)
+constexpr int kNearNone = 0, kNearValid = 1, kNearDense = 2;
+// step_w64_body's near_ctl
+constexpr int kNearCtlKeep = 1;   // the state of the step before is this env's (not a launch's first step)
+constexpr int kNearCtlPlain = 2;  // MACM_DEBUG_NEAR_PLAIN
+// what a step did, for the stamp build
+constexpr int kNearKindPlain = 0, kNearKindList = 1, kNearKindRebuild = 2;
+
+// mask = (mask << 1) | (d2 <= thr2): one compare and one add-with-carry per record
+__device__ __forceinline__ void near_push(float d2, float thr2, uint32_t& mask) {
+  asm volatile(
+      "v_cmp_le_f32 vcc, %1, %2\n\t"
+      "v_addc_co_u32 %0, vcc, %0, %0, vcc"
+      : "+v"(mask)
+      : "v"(d2), "v"(thr2)
+      : "vcc");
+}
+
+// (B): the candidate mask of this lane, records taken 63 .. 32 and 31 .. 0 so that record j ends at
+// bit j of its word; fl_d2 as near2_min's scalar form
+__device__ __forceinline__ unsigned long long near_build(const float4* s_pc2, fvec2 cme, float thr2) {
+  uint32_t lo = 0u, hi = 0u;
+  float4 na = s_pc2[15], nb = s_pc2[31];  // one position pair of each half ahead, as the sweep's window
+#pragma unroll 4
+  for (int k = 15; k >= 0; --k) {
+    const float4 qa = na, qb = nb;
+    if (k > 0) {
+      na = s_pc2[k - 1];
+      nb = s_pc2[15 + k];
+    }
+    const float ax1 = qa.z - cme.x, ay1 = qa.w - cme.y, bx1 = qb.z - cme.x, by1 = qb.w - cme.y;
+    const float ax0 = qa.x - cme.x, ay0 = qa.y - cme.y, bx0 = qb.x - cme.x, by0 = qb.y - cme.y;
+    near_push(ax1 * ax1 + ay1 * ay1, thr2, lo);
+    near_push(bx1 * bx1 + by1 * by1, thr2, hi);
+    near_push(ax0 * ax0 + ay0 * ay0, thr2, lo);
+    near_push(bx0 * bx0 + by0 * by0, thr2, hi);
+  }
+  return (unsigned long long)lo | ((unsigned long long)hi << 32);
+}
+
+// The list step: every lane walks its own mask in ascending j (strict '<': the lowest index wins
+// ties, mvmnt.py:194) and reads s_pc[j] by its own index, two entries a trip so that their LDS reads
+// are in flight together; the wave's trip count is half the largest list. A lane whose list has
+// ended reads its own record and takes nothing.
+__device__ __forceinline__ void near_list(const float2* s_pc, unsigned long long m, fvec2 cme, int lane, float& best,
+                                          int& bj) {
+  while (__builtin_amdgcn_ballot_w64(m != 0ull) != 0ull) {
+    const bool more0 = m != 0ull;
+    const int j0 = more0 ? (int)__builtin_ctzll(m) : lane;
+    m &= m - 1ull;
+    const bool more1 = m != 0ull;
+    const int j1 = more1 ? (int)__builtin_ctzll(m) : lane;
+    m &= m - 1ull;
+    const float2 q0 = s_pc[j0], q1 = s_pc[j1];
+    const float dx0 = q0.x - cme.x, dy0 = q0.y - cme.y, dx1 = q1.x - cme.x, dy1 = q1.y - cme.y;
+    const float d20 = dx0 * dx0 + dy0 * dy0, d21 = dx1 * dx1 + dy1 * dy1;
+    if (more0 && d20 < best) {
+      best = d20;
+      bj = j0;
+    }
+    if (more1 && d21 < best) {
+      best = d21;
+      bj = j1;
+    }
+  }
+}
+
 // ---- overlaps of the moved proxies ---------------------------------------------------------------
 // b2BroadPhase::UpdatePairs queries only the proxies that MoveProxy buffered, i.e. the bodies whose
 // fat AABB SynchronizeFixtures rewrote this step (movedm). For a pair with neither proxy moved the
@@ -899,15 +1003,18 @@ struct StepCarry {
 // CARRY (Flock rollouts with given actions): `carry` is in/out (StepCarry); `actions_next` is the next
 // step's actions, loaded into it while this step runs (NULL at a launch's last step: there is no row
 // to read).
-template <int MODE, int NCAP, typename OT, bool SCAL = false, bool CARRY = false>
+// NEARL (Flock rollouts, NCAP = 64): the nearest neighbour from the candidate lists kept in LDS between
+// the steps of a launch (above near_build); near_ctl: kNearCtl* bits.
+template <int MODE, int NCAP, typename OT, bool SCAL = false, bool CARRY = false, bool NEARL = false>
 __device__ __attribute__((always_inline)) inline void step_w64_body(
     const StepParams& P, const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur,
     const void* __restrict__ actions, OT* __restrict__ obs, int32_t* __restrict__ nbr_out,
     float* __restrict__ rew_out, uint8_t* __restrict__ coll_out, uint8_t* __restrict__ done_out,
     const int e = blockIdx.x, const int lane = threadIdx.x, TailObs* tl = nullptr, StepCarry* carry = nullptr,
-    const void* actions_next = nullptr, void** pool_out = nullptr) {
+    const void* actions_next = nullptr, void** pool_out = nullptr, const int near_ctl = 0) {
   constexpr bool kT = MODE == kTdm;
   static_assert(!CARRY || !kT, "the carried step is Flock's");
+  static_assert(!NEARL || (!kT && NCAP == 64), "the candidate lists are the 64-record Flock sweep's");
 #ifdef MACM_TIMELINE
   const unsigned long long tl_rt0 = __builtin_amdgcn_s_memrealtime(), tl_c0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -972,8 +1079,14 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
   __shared__ double s_hpd[W];
   __shared__ int8_t s_hit[W];
   __shared__ float s_ang[W];
+  // NEARL only (unreferenced, hence not allocated, elsewhere): per lane its candidate mask and build
+  // position, read and written by that lane alone, and the wave-uniform list state; they live from
+  // one step of a launch to the next, so they overlay nothing
+  __shared__ uint4 s_nl[NEARL ? W : 1];
+  __shared__ int s_nl_state, s_nl_retry;  // s_nl_retry: the plain steps after the last failed rebuild (0: none failed)
 #ifdef MACM_STAMPS
   __shared__ int s_stat_maxisl;
+  int stat_near = 0;  // kNearKind* | the largest list << 8
 #endif
   if constexpr (kT) {
     if (tl && tl->worker) {  // the tail observation: one (step, env) row instead of a step
@@ -1087,6 +1200,12 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
     }
   }
   s_c[lane] = p;
+  if constexpr (NEARL) {
+    if (!(near_ctl & kNearCtlKeep)) {  // a launch's first step, the step after an in-launch reset: no list
+      s_nl_state = kNearNone;
+      s_nl_retry = 0;
+    }
+  }
   if (lane < TCAP / 32) s_cvis[lane] = 0u;
   s_oldm[2 * lane] = 0u;
 #pragma unroll
@@ -1308,6 +1427,7 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
         if (carried) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         carry->valid = false;
       }
+      if constexpr (NEARL) s_nl_state = kNearNone;  // a spill step clears the lists
       spill::step_env<OT, true>(P, B, e, cur, actions, obs, nbr_out, rew_out, coll_out, done_out,
                                 reinterpret_cast<unsigned char*>(&s_pool));
       return;
@@ -2029,7 +2149,36 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
   int bj = lane == 0 ? 1 : 0;
   if constexpr (!kT) {
     const float4* const s_pc2 = reinterpret_cast<const float4*>(s_pc);
-    if constexpr (NCAP == 64) {  // two interleaved chains
+    // NEARL: what this step does (wave-uniform) and the state it leaves
+    int nkind = kNearKindPlain;
+    uint4 nl = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (NEARL) {
+      const int nst = __builtin_amdgcn_readfirstlane(s_nl_state);
+      int nnext = kNearNone;
+      if ((near_ctl & kNearCtlPlain) || N < 2) {
+      } else if (nst >= kNearDense) {
+        nnext = nst == kNearDense ? kNearNone : nst - 1;
+      } else if (CARRY && !carried) {
+        // the step before ended the carry (or there was none): the lists are cleared, and built
+        // again by a carried step only (an env that loads every step would rebuild every step)
+      } else {
+        nkind = kNearKindRebuild;
+        nnext = kNearValid;
+        if (nst == kNearValid) {  // (V)
+          nl = s_nl[lane];
+          const float mx = cx - __uint_as_float(nl.z), my = cy - __uint_as_float(nl.w);
+          const float m2 = mx * mx + my * my;
+          if (__builtin_amdgcn_ballot_w64(act && !(m2 <= kNearMove2)) == 0ull) nkind = kNearKindList;
+        }
+      }
+      s_nl_state = nnext;  // (a rebuild whose lists exceed the cap: dense, below)
+    }
+    if (NEARL && nkind == kNearKindList) {
+      near_list(s_pc, (unsigned long long)nl.x | ((unsigned long long)nl.y << 32), mk2(cx, cy), lane, best, bj);
+#ifdef MACM_STAMPS
+      stat_near = kNearKindList | (wave_max(__popc(nl.x) + __popc(nl.y)) << 8);
+#endif
+    } else if constexpr (NCAP == 64) {  // two interleaved chains
       NearState2 s2;
       s2.best_a = __builtin_inff();
       s2.best_b = __builtin_inff();
@@ -2045,6 +2194,25 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
       const bool upper = s2.best_b < s2.best_a;  // the lower half wins ties (lower indices)
       best = upper ? s2.best_b : s2.best_a;
       bj = upper ? s2.bj_b : s2.bj_a;
+      if constexpr (NEARL) {
+        if (nkind == kNearKindRebuild) {  // (B)
+          const float t = __builtin_amdgcn_sqrtf(best) + kNearS;
+          unsigned long long m = near_build(s_pc2, mk2(cx, cy), t * t * kNearPad) & ~(1ull << lane);
+          if (!act) m = 0ull;
+          const int cnt = __popcll(m);
+          int retry = 0;
+          if (__builtin_amdgcn_ballot_w64(cnt > kNearCap) != 0ull) {
+            const int prev = __builtin_amdgcn_readfirstlane(s_nl_retry);
+            retry = prev == 0 ? kNearRetry : (2 * prev < kNearRetryMax ? 2 * prev : kNearRetryMax);
+            s_nl_state = kNearDense + retry - 1;
+          }
+          s_nl_retry = retry;
+          s_nl[lane] = make_uint4((uint32_t)m, (uint32_t)(m >> 32), __float_as_uint(cx), __float_as_uint(cy));
+#ifdef MACM_STAMPS
+          stat_near = kNearKindRebuild | (wave_max(cnt) << 8);
+#endif
+        }
+      }
     } else {
       NearState s1;
       s1.best = best;
@@ -2283,6 +2451,9 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
     // raises a status bit ends the carry too: the launch is about to be reported as failed.
     carry->valid = total <= RCH * W && !(mst1 | mst2 | mst4);
   }
+  if constexpr (NEARL) {
+    if (mst1 | mst2 | mst4) s_nl_state = kNearNone;  // a step that raises a status bit clears the lists
+  }
   STAMP(13);
 #ifdef MACM_TIMELINE
   {
@@ -2301,7 +2472,7 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
 #endif
   STAMP_STAT(14, (unsigned long long)T | ((unsigned long long)nisl << 16) | ((unsigned long long)M << 32));
 #ifdef MACM_STAMPS
-  STAMP_STAT(15, (unsigned long long)s_stat_maxisl | ((unsigned long long)total << 32));
+  STAMP_STAT(15, (unsigned long long)s_stat_maxisl | ((unsigned long long)stat_near << 16) | ((unsigned long long)total << 32));
 #endif
 }
 
@@ -2485,6 +2656,8 @@ struct RolloutArgs {  // the kernel's only argument (kernarg offset 0)
 // step loads its state and waits for the stores of the step before, as a rollout without the carry.
 // (Not a field of its own: the argument layout of the other rollout kernels stays the measured one.)
 constexpr int kRollReloadBit = 2;
+// Flock rollouts, NCAP = 64: MACM_DEBUG_NEAR_PLAIN in the same word, every step takes the plain sweep
+constexpr int kRollNearPlainBit = 4;
 
 // [K, ...] row k of an output (trajectory form); NULL stays NULL
 template <typename T>
@@ -2598,23 +2771,27 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
     int sl = (int)threadIdx.x;
     if constexpr (MODE == kTdm) asm volatile("" : "+v"(sl));
     tl.k = k - A0.tail_k0;
+    // the candidate lists of the nearest-neighbour sweep (near_build): Flock with 64 records
+    constexpr bool kNearL = MODE == kFlock && NCAP == 64;
+    const int near_ctl = kNearL ? (k > 0 ? kNearCtlKeep : 0) | ((A.cur & kRollNearPlainBit) ? kNearCtlPlain : 0) : 0;
     if constexpr (CARRY) {
       const unsigned char* const act_k = static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride;
-      step_w64_body<MODE, NCAP, OT, SCAL, true>(A.P, A.B, A.TP, TB, (A.cur ^ k) & 1, act_k, obs,
-                                                traj_row(A.nbr_out, kr, EN), traj_row(A.rew_out, kr, EN),
-                                                traj_row(A.coll_out, kr, EN), traj_row(A.done_out, kr, (size_t)A.P.n_envs),
-                                                env, sl, nullptr, &cy, k + 1 < ksteps ? act_k + A.astride : nullptr);
+      step_w64_body<MODE, NCAP, OT, SCAL, true, kNearL>(
+          A.P, A.B, A.TP, TB, (A.cur ^ k) & 1, act_k, obs, traj_row(A.nbr_out, kr, EN), traj_row(A.rew_out, kr, EN),
+          traj_row(A.coll_out, kr, EN), traj_row(A.done_out, kr, (size_t)A.P.n_envs), env, sl, nullptr, &cy,
+          k + 1 < ksteps ? act_k + A.astride : nullptr, nullptr, near_ctl);
       if (A.cur & kRollReloadBit) cy.valid = false;
       // only a step that loads reads what this wave stored (workgroup scope: below); the barrier
       // orders the LDS reuse
       if (!cy.valid) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __syncthreads();
     } else {
-      step_w64_body<MODE, NCAP, OT, SCAL>(A.P, A.B, A.TP, TB, A.cur ^ (k & 1),
-                                          pol_in ? pol_in : static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride,
-                                          obs, traj_row(A.nbr_out, kr, EN), traj_row(A.rew_out, kr, EN),
-                                          traj_row(A.coll_out, kr, EN), traj_row(A.done_out, kr, (size_t)A.P.n_envs),
-                                          env, sl, MODE == kTdm ? &tl : nullptr);
+      step_w64_body<MODE, NCAP, OT, SCAL, false, kNearL>(
+          A.P, A.B, A.TP, TB, kNearL ? (A.cur ^ k) & 1 : A.cur ^ (k & 1),
+          pol_in ? pol_in : static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride, obs,
+          traj_row(A.nbr_out, kr, EN), traj_row(A.rew_out, kr, EN), traj_row(A.coll_out, kr, EN),
+          traj_row(A.done_out, kr, (size_t)A.P.n_envs), env, sl, MODE == kTdm ? &tl : nullptr, nullptr, nullptr, nullptr,
+          near_ctl);
       // the next step reads only what this wave wrote: workgroup scope (this CU's L1 and its XCD's L2)
       // suffices; agent scope would write back and invalidate the L2 every step (5x slower, measured)
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -2676,7 +2853,7 @@ static void launch_roll(int nsteps, unsigned long long astride, int traj, hipStr
                         const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur, const void* actions,
                         void* obs, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done,
                         unsigned long long* tail_ctl = nullptr, unsigned tail_tag = 0u, int tail_workers = 0,
-                        int tail_k0 = 0, int reload = 0) {
+                        int tail_k0 = 0, int reload = 0) {  // reload: bit 0 MACM_DEBUG_ROLLOUT_RELOAD, bit 1 _NEAR_PLAIN
   // astride == 0: closed loop, `actions` is the bots' action buffer (macm_world_rollout_bots)
   uint8_t* pol = astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(actions)) : nullptr;
   const bool bal = B.sched && nsteps >= kRollBalanceMinSteps;
@@ -2693,10 +2870,12 @@ static void launch_roll(int nsteps, unsigned long long astride, int traj, hipStr
   const int blocks = P.n_envs + (tail_tag ? tail_workers : 0);
   if constexpr (MODE == kFlock) {
     if (!pol) {  // actions given: the carried step
-      if (reload) A.cur |= kRollReloadBit;
+      if (reload & 1) A.cur |= kRollReloadBit;
+      if (NCAP == 64 && (reload & 2)) A.cur |= kRollNearPlainBit;
       hipLaunchKernelGGL((env_rollout_w64<MODE, NCAP, OT, SCAL, true>), dim3(blocks), dim3(W), 0, s, A);
       return;
     }
+    if (NCAP == 64 && (reload & 2)) A.cur |= kRollNearPlainBit;
   }
   hipLaunchKernelGGL((env_rollout_w64<MODE, NCAP, OT, SCAL>), dim3(blocks), dim3(W), 0, s, A);
 }

@@ -116,7 +116,9 @@ struct macm_world {
   bool ho_tried = false;
   int slots_alloc = 0;  // spill working-set slots allocated (== E: one per env)
   int pool0 = 0;        // B.sp_pool as created (0: one slot per env), restored by set_debug
-  int roll_reload = 0;  // MACM_DEBUG_ROLLOUT_RELOAD: wave rollouts load and fence every step
+  // wave rollouts: bit 0 MACM_DEBUG_ROLLOUT_RELOAD (load and fence every step), bit 1 MACM_DEBUG_NEAR_PLAIN
+  // (the plain nearest-neighbour sweep every step)
+  int roll_reload = 0;
 };
 
 struct macm_tdm {
@@ -1187,13 +1189,13 @@ int macm_world_set_debug(macm_world* w, int32_t flags) {
   const int pool = (flags & MACM_DEBUG_SPILL_POOL) ? (flags >> 8) : 0;
   flags &= 0xff;
   if (flags & ~(MACM_DEBUG_FORCE_SPILL | MACM_DEBUG_SWEEP_CELLS | MACM_DEBUG_SWEEP_ALL_PAIRS | MACM_DEBUG_SPILL_POOL | MACM_DEBUG_SPILL_FAIL |
-                MACM_DEBUG_ROLLOUT_RELOAD))
+                MACM_DEBUG_ROLLOUT_RELOAD | MACM_DEBUG_NEAR_PLAIN))
     return fail(MACM_E_INVALID, "unknown debug flag");
   if ((flags & MACM_DEBUG_SWEEP_CELLS) && (flags & MACM_DEBUG_SWEEP_ALL_PAIRS))
     return fail(MACM_E_INVALID, "SWEEP_CELLS and SWEEP_ALL_PAIRS exclude each other");
   if (int rc = set_spill_pool(w, flags, pool)) return rc;
   w->P.force_spill = (flags & MACM_DEBUG_FORCE_SPILL) ? 1 : 0;
-  w->roll_reload = (flags & MACM_DEBUG_ROLLOUT_RELOAD) ? 1 : 0;
+  w->roll_reload = ((flags & MACM_DEBUG_ROLLOUT_RELOAD) ? 1 : 0) | ((flags & MACM_DEBUG_NEAR_PLAIN) ? 2 : 0);
   w->P.sweep = (flags & MACM_DEBUG_SWEEP_CELLS) ? 1 : (flags & MACM_DEBUG_SWEEP_ALL_PAIRS) ? 2 : 0;
   return MACM_OK;
 }

@@ -149,6 +149,9 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
   const bool bal = R0.A.B.sched && nsteps >= kRollBalanceMinSteps;  // as in launch_roll_ar
   const int env = bal ? (int)R0.A.B.sched[R0.A.sched_off + blockIdx.x] : (int)blockIdx.x;
   StepCarry cy{};  // CARRY; not valid: the first step loads
+  // the candidate lists of the nearest-neighbour sweep (near_build); an in-launch reset clears them
+  constexpr bool kNearL = MODE == kFlock && NCAP == 64;
+  int near_keep = 0;
   for (int k = 0; k < nsteps; ++k) {
     // as env_rollout_w64: the arguments afresh every step, through a pointer the compiler cannot see through
     const __attribute__((address_space(4))) RolloutArArgs<OT>* ka =
@@ -175,18 +178,19 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
     int sl = (int)threadIdx.x;
     if constexpr (MODE == kTdm) asm volatile("" : "+v"(sl));
     void* lds = nullptr;  // the step's contact pool, dead once the step ends
+    const int near_ctl = kNearL ? near_keep | ((A.cur & kRollNearPlainBit) ? kNearCtlPlain : 0) : 0;
     if constexpr (CARRY) {
       const unsigned char* const act_k = static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride;
-      step_w64_body<MODE, NCAP, OT, SCAL, true>(A.P, A.B, A.TP, TB, (A.cur ^ k) & 1, act_k, obs, nbr,
-                                                traj_row(A.rew_out, kr, EN), traj_row(A.coll_out, kr, EN),
-                                                traj_row(A.done_out, kr, (size_t)A.P.n_envs), env, sl, nullptr, &cy,
-                                                k + 1 < nsteps ? act_k + A.astride : nullptr, &lds);
+      step_w64_body<MODE, NCAP, OT, SCAL, true, kNearL>(
+          A.P, A.B, A.TP, TB, (A.cur ^ k) & 1, act_k, obs, nbr, traj_row(A.rew_out, kr, EN), traj_row(A.coll_out, kr, EN),
+          traj_row(A.done_out, kr, (size_t)A.P.n_envs), env, sl, nullptr, &cy,
+          k + 1 < nsteps ? act_k + A.astride : nullptr, &lds, near_ctl);
     } else {
-      step_w64_body<MODE, NCAP, OT, SCAL>(A.P, A.B, A.TP, TB, A.cur ^ (k & 1),
-                                          pol_in ? pol_in : static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride,
-                                          obs, nbr, traj_row(A.rew_out, kr, EN), traj_row(A.coll_out, kr, EN),
-                                          traj_row(A.done_out, kr, (size_t)A.P.n_envs), env, sl, nullptr, nullptr, nullptr,
-                                          &lds);
+      step_w64_body<MODE, NCAP, OT, SCAL, false, kNearL>(
+          A.P, A.B, A.TP, TB, kNearL ? (A.cur ^ k) & 1 : A.cur ^ (k & 1),
+          pol_in ? pol_in : static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride, obs, nbr,
+          traj_row(A.rew_out, kr, EN), traj_row(A.coll_out, kr, EN), traj_row(A.done_out, kr, (size_t)A.P.n_envs), env, sl,
+          nullptr, nullptr, nullptr, &lds, near_ctl);
     }
     // the step's done flag, wave-uniform once broadcast from lane 0, which stored it (a lane's
     // accesses to one address stay in order)
@@ -197,6 +201,7 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
     int dn = 0;
     if (rl == 0) dn = A.B.done[env];
     dn = __builtin_amdgcn_readfirstlane(dn);
+    if constexpr (kNearL) near_keep = dn ? 0 : kNearCtlKeep;
     if constexpr (CARRY) {
       if (dn || (A.cur & kRollReloadBit)) cy.valid = false;
       if (!cy.valid) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -247,10 +252,12 @@ static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hip
                       D};
   if constexpr (MODE == kFlock) {
     if (!pol) {  // actions given: the carried step
-      if (reload) R.A.cur |= kRollReloadBit;
+      if (reload & 1) R.A.cur |= kRollReloadBit;
+      if (NCAP == 64 && (reload & 2)) R.A.cur |= kRollNearPlainBit;
       hipLaunchKernelGGL((env_rollout_ar_w64<MODE, NCAP, OT, SCAL, true>), dim3(P.n_envs), dim3(W), 0, s, R);
       return;
     }
+    if (NCAP == 64 && (reload & 2)) R.A.cur |= kRollNearPlainBit;
   }
   hipLaunchKernelGGL((env_rollout_ar_w64<MODE, NCAP, OT, SCAL>), dim3(P.n_envs), dim3(W), 0, s, R);
 }

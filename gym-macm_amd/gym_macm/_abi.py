@@ -22,6 +22,7 @@ DEBUG_SWEEP_ALL_PAIRS = 4
 DEBUG_SPILL_POOL = 8  # | slots << 8
 DEBUG_SPILL_FAIL = 16  # no spill slot is ever free (SPILL_WAIT test hook)
 DEBUG_ROLLOUT_RELOAD = 32  # wave rollouts load the state every step (no register carry)
+DEBUG_NEAR_PLAIN = 64  # Flock wave rollouts: the all-pairs nearest-neighbour sweep every step (no candidate lists)
 E_INVALID, E_OVERFLOW = -1, -5
 
 _ERRORS = {

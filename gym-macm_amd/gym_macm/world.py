@@ -433,7 +433,9 @@ class World:
         spill step; DEBUG_SWEEP_CELLS / DEBUG_SWEEP_ALL_PAIRS pick the workgroup path's pair sweep
         regardless of N (default: strip cells from N = 256); DEBUG_SPILL_POOL | slots << 8 shares
         that many working-set slots; DEBUG_SPILL_FAIL makes every slot request fail (the env is left
-        unstepped with ST_SPILL_WAIT)."""
+        unstepped with ST_SPILL_WAIT); DEBUG_ROLLOUT_RELOAD makes every step of a wave rollout load
+        its state; DEBUG_NEAR_PLAIN makes every step of one take the all-pairs nearest-neighbour
+        sweep instead of the candidate lists."""
         _abi.check(self.L.macm_world_set_debug(self.h, int(flags)), "macm_world_set_debug")
 
     def check_status(self) -> None:

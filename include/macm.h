@@ -90,8 +90,10 @@ enum {
                                      the slots allocated (pooled-slot tests at small E)            */
   MACM_DEBUG_SPILL_FAIL = 16,     /* no spill slot is ever free: every env that needs the spill step
                                      is left unstepped with MACM_ST_SPILL_WAIT (ABI 8 test hook)   */
-  MACM_DEBUG_ROLLOUT_RELOAD = 32  /* wave rollouts: every step loads its state from global memory
+  MACM_DEBUG_ROLLOUT_RELOAD = 32, /* wave rollouts: every step loads its state from global memory
                                      behind a fence, none is carried in registers (A/B, tests)     */
+  MACM_DEBUG_NEAR_PLAIN = 64      /* Flock wave rollouts: every step takes the all-pairs nearest-
+                                     neighbour sweep, none the candidate lists (A/B, tests)        */
 };
 
 /*

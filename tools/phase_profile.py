@@ -1,6 +1,12 @@
 """Per-phase cycle shares of flock_step_w64 from the diagnostic stamp build.
 
     make -C gym-macm_amd stamps && python tools/phase_profile.py [--envs 4096] [--steps 20]
+    python tools/phase_profile.py --launch rollout [--launch-steps 48]
+
+--launch rollout (N <= 64, random actions): every sample is the last step of a rollout launch of
+--launch-steps + sample index steps, the only form in which the nearest neighbour comes from the
+candidate lists (near_build in csrc/flock_step_w64.hip); the `near` block gives the fractions of list,
+rebuild and plain steps, the largest list and the `pairs+nearest` cycles of each kind.
 
 Loads build/libmacm_hip_stamps.so (in-kernel s_memtime at phase boundaries; see
 STAMP() in csrc/flock_step_w64.hip). Read SHARES, not absolute time: the stamps'
@@ -47,6 +53,10 @@ def main():
     ap.add_argument("--spread", type=float, default=20.0)
     ap.add_argument("--policy", choices=("random", "bots"), default="random")
     ap.add_argument("--flocks", type=int, default=1, help="targets = i * flocks // N (config 3: 4)")
+    ap.add_argument("--launch", choices=("step", "rollout"), default="step")
+    ap.add_argument("--launch-steps", type=int, default=48,
+                    help="--launch rollout: steps of the first sampled launch (long enough for the envs' rebuilds, "
+                         "which a launch starts together, to spread out)")
     ap.add_argument("--json", default="")
     args = ap.parse_args()
     L = _abi.lib()
@@ -59,8 +69,16 @@ def main():
     gen.manual_seed(1)
     buf = np.zeros((E, 32), np.uint64)
     deltas, stats, walls, stats_wg = [], [], [], []
-    for s in range(args.warmup + args.steps):
-        if args.policy == "bots":
+    roll = args.launch == "rollout"
+    if roll and (N > 64 or args.policy != "random"):
+        ap.error("--launch rollout: the wave path with random actions")
+    if roll:  # the warm-up in one launch; then one launch per sample
+        vec.rollout(torch.randint(0, 3, (args.warmup, E, N, 3), dtype=torch.uint8, device="cuda:0", generator=gen))
+    for s in range(args.warmup if roll else 0, args.warmup + args.steps):
+        if roll:
+            a = torch.randint(0, 3, (args.launch_steps + s - args.warmup, E, N, 3), dtype=torch.uint8, device="cuda:0",
+                              generator=gen)
+        elif args.policy == "bots":
             from gym_macm.bots import flock_actions
             a = flock_actions(vec.obs)
         else:
@@ -69,7 +87,10 @@ def main():
             torch.cuda.synchronize()
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        vec.step(a)
+        if roll:
+            vec.rollout(a)
+        else:
+            vec.step(a)
         if s >= args.warmup:
             ev1.record()
             torch.cuda.synchronize()
@@ -93,7 +114,8 @@ def main():
     phases = PHASES if N <= 64 else PHASES_A + PHASES_C + PHASES_B + PHASES_D
     st = np.concatenate(stats)
     total = d.sum(axis=1)
-    out = {"envs": E, "agents": N, "spread": args.spread, "policy": args.policy, "kernel_ms_stamped": float(np.mean(walls)),
+    out = {"envs": E, "agents": N, "spread": args.spread, "policy": args.policy, "launch": args.launch,
+           "kernel_ms_stamped": float(np.mean(walls)),
            "wave_cycles_mean": float(total.mean()), "wave_cycles_p95": float(np.percentile(total, 95)),
            "wave_cycles_max": float(total.max()), "phases": {}}
     for k, name in enumerate(phases):
@@ -146,7 +168,18 @@ def main():
     T = (st[:, 0] & 0xFFFF).astype(np.int64)
     nisl = ((st[:, 0] >> 16) & 0xFFFF).astype(np.int64)
     M = (st[:, 0] >> 32).astype(np.int64)
-    maxisl = (st[:, 1] & 0xFFFFFFFF).astype(np.int64)
+    maxisl = (st[:, 1] & 0xFFFF).astype(np.int64)
+    # the nearest neighbour of the step: 0 plain sweep, 1 list step, 2 rebuild; the env's largest list
+    nkind = ((st[:, 1] >> 16) & 0xFF).astype(np.int64)
+    nlargest = ((st[:, 1] >> 24) & 0xFF).astype(np.int64)
+    pn = d[:, phases.index("pairs+nearest")]
+    out["near"] = {}
+    for k, name in enumerate(("plain", "list", "rebuild")):
+        sel = nkind == k
+        out["near"][name] = {"frac": float(sel.mean()),
+                             "pairs+nearest_cycles_mean": float(pn[sel].mean()) if sel.any() else None,
+                             "largest_list_mean": float(nlargest[sel].mean()) if sel.any() and k else None,
+                             "largest_list_p95": float(np.percentile(nlargest[sel], 95)) if sel.any() and k else None}
     cnt = (st[:, 1] >> 32).astype(np.int64)
     for name, v in (("touching", T), ("islands", nisl), ("list_in", M), ("max_island_contacts", maxisl),
                     ("list_out", cnt)):
