@@ -41,6 +41,9 @@ struct StepParams {
   float radius;      // circle radius
   float friction;    // b2MixFriction = sqrtf(f * f)
   float force_f32;   // (float)agent_force (continuous mode: numpy float32 * int)
+  // binary reward: d < reward_radius for d = sqrt((double)td2) exactly when td2 < reward_thr2
+  // (reward_threshold.h; in the four bytes that padded rot_step, so no other field moves)
+  float reward_thr2;
   double rot_step;   // rotation_speed, multiplied as ((a2-1) * rot) * (1/hz)   mvmnt.py:103-104
   double inv_hz;     // 1 / hz (Python float division)                       mvmnt.py:104,134
   double force;      // agent_force (double)                                 mvmnt.py:113-116
@@ -234,9 +237,11 @@ __host__ __device__ inline int tdm_team_of(const TdmParams& T, int i) {
 // macm_action_trig (macm_math.h; its derived float32 forces and ray offsets equal glibc's
 // for every float32 angle |a| < 2^19, tools/trig_check.c) in that range, the device libm
 // beyond it (|angle| >= 2^19 only arises from injected state: the step wraps into [-pi, pi]).
+// KSPIN: the polynomial constants from scalar registers (MACM_KS, macm_math.h), the same results.
+template <bool KSPIN = false>
 __device__ __forceinline__ void act_trig(float a, double* s0, double* c0, double* s1, double* c1) {
   if (fabsf(a) < 524288.0f) {
-    macm_action_trig(a, s0, c0, s1, c1);
+    MACM_KS_FN(macm_action_trig, KSPIN)(a, s0, c0, s1, c1);
   } else {
     sincos((double)a, s0, c0);
     sincos((double)a + M_PI / 2, s1, c1);

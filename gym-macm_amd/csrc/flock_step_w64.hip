@@ -54,6 +54,13 @@
 #include "flock_spill.hpp"
 #include "tdm_obs.hpp"
 
+// (a translation unit that defines MACM_KS_SWITCH, macm_math.h, pins in its Flock steps; TDM never)
+#ifdef MACM_KS_SWITCH
+#define MACM_KS_PIN_FLOCK true
+#else
+#define MACM_KS_PIN_FLOCK false
+#endif
+
 namespace macm {
 
 constexpr int W = 64;       // wavefront = one env's agent lanes
@@ -200,13 +207,13 @@ __device__ __forceinline__ void write_obs_row(OT* o, int coord, double r0, doubl
 // Flock.get_obs for one agent (mvmnt.py:181-222): node 0 = closest other agent
 // (squared distance `best`, relative position (rx, ry) = other - self, float32),
 // node 1 = the agent's target (relative position target - self, float32).
-template <typename OT>
+template <typename OT, bool KSPIN = false>
 __device__ __forceinline__ void write_obs(OT* o, int coord, float ang, float best, float rx, float ry, float tdx,
                                           float tdy, float td2) {
   // obs_atan2 (macm_math.h): <= 1 ulp from glibc atan2 in f64, identical after "- angle"
   // and the float32 rounding (tools/atan2_check.c), about half the device libm's work
-  const double t0 = wrap_pi(obs_atan2((double)ry, (double)rx) - (double)ang);
-  const double t1 = wrap_pi(obs_atan2((double)tdy, (double)tdx) - (double)ang);
+  const double t0 = wrap_pi(MACM_KS_FN(obs_atan2, KSPIN)((double)ry, (double)rx) - (double)ang);
+  const double t1 = wrap_pi(MACM_KS_FN(obs_atan2, KSPIN)((double)tdy, (double)tdx) - (double)ang);
   write_obs_row(o, coord, obs_sqrt<OT>(best), t0, obs_sqrt<OT>(td2), t1);
 }
 
@@ -744,6 +751,9 @@ constexpr int kNearNone = 0, kNearValid = 1, kNearDense = 2;
 // step_w64_body's near_ctl
 constexpr int kNearCtlKeep = 1;   // the state of the step before is this env's (not a launch's first step)
 constexpr int kNearCtlPlain = 2;  // MACM_DEBUG_NEAR_PLAIN
+// in the same word, carried steps (StepCarry): this step writes its state back whatever follows it
+// (MACM_DEBUG_ROLLOUT_RELOAD: the next step loads)
+constexpr int kStepCtlWriteBack = 4;
 // what a step did, for the stamp build
 constexpr int kNearKindPlain = 0, kNearKindList = 1, kNearKindRebuild = 2;
 
@@ -831,8 +841,9 @@ __device__ __forceinline__ unsigned long long moved_pairs(unsigned long long mov
 
 // New-pair compaction in descending (a, b) order: lane a owns the bitmask of
 // partners b > a. Returns the total count; writes at most C entries.
-// stage_ab / stage_im (LDS, RCH * W entries; NULL: none): a copy of the entries below RCH * W, which a
-// carried rollout step hands to the next step in registers (StepCarry).
+// stage_ab / stage_im (LDS, RCH * W entries; NULL: none): the entries below RCH * W go there and not
+// to global memory: a carried rollout step hands them to the next step in registers and writes them
+// out itself where something will read them (StepCarry).
 __device__ __forceinline__ int write_new_pairs(int lane, unsigned long long newmask, uint32_t* ocab,
                                                float2* ocimp, int C, uint32_t* stage_ab = nullptr,
                                                float2* stage_im = nullptr) {
@@ -845,11 +856,12 @@ __device__ __forceinline__ int write_new_pairs(int lane, unsigned long long newm
     const int j = 63 - __clzll(m);
     m &= ~(1ull << j);
     if (w < C) {
-      st_g<kState>(ocab + w, (uint32_t)lane | ((uint32_t)j << 16));
-      st_g<kState>(ocimp + w, make_float2(0.0f, 0.0f));
       if (stage_ab && w < RCH * W) {
         stage_ab[w] = (uint32_t)lane | ((uint32_t)j << 16);
         stage_im[w] = make_float2(0.0f, 0.0f);
+      } else {
+        st_g<kState>(ocab + w, (uint32_t)lane | ((uint32_t)j << 16));
+        st_g<kState>(ocimp + w, make_float2(0.0f, 0.0f));
       }
     }
     ++w;
@@ -974,12 +986,15 @@ __device__ __forceinline__ void tdm_tail_row(const StepParams& P, const WorldBuf
 }
 
 // What a Flock rollout's wave keeps in registers from one step to the next (env_rollout_w64, CARRY):
-// exactly the values the next step's up-front loads would return, each taken from what this step
-// stores, so a carried step starts without a global load and the step before it need not wait for
-// its stores. The step still stores everything, so global memory after any step is what a
-// one-step launch leaves. `valid` (wave-uniform) is false at a launch's first step, after a spill
-// step, a raised status bit or a list longer than the RCH register chunks: the next step then loads
-// as a one-step launch does, behind the workgroup fence that the rollout loop takes in that case.
+// exactly the values the next step's up-front loads would return, so a carried step starts without
+// a global load. Lane 0's per-env values travel beside it in LDS (EnvCarry). A step that a carried
+// step follows stores its outputs only: the env's state rows, list and per-env words are written
+// where something will read them (step_w64_body's wb), so global memory after a launch, not after
+// each of its steps, is what one-step launches leave. `valid` (wave-uniform) is false at a launch's
+// first step, after a spill step, a raised status bit or a list longer than the RCH register chunks:
+// the step before wrote everything back, and the next step loads as a one-step launch does, behind
+// the workgroup fence that the rollout loop takes in that case. (A carried step never needs the spill
+// step, which reads global memory: see the hand-over.)
 struct StepCarry {
   bool valid;
   float2 p, v, tg;
@@ -991,6 +1006,15 @@ struct StepCarry {
   // nothing waits for them here): discrete a0 | a1 << 8 and a2, or the bits of the continuous (x, y)
   uint32_t ar0, ar1;
   int M, step_count;  // wave-uniform
+};
+
+// Lane 0's side of the carry: the per-env values that the step's last lines update, in LDS that
+// nothing overlays, read and written by lane 0 alone (no address arithmetic, no vmcnt).
+struct __align__(16) EnvCarry {
+  unsigned long long ctr[4];  // env_counters
+  double time_passed;
+  double rsum;  // env_rsum (linear reward): the running total, the steps' sums added in step order
+  int status;
 };
 
 // MODE kFlock: Flock.step. MODE kTdm: TDM.step (combat.py:104-184) — the same
@@ -1013,6 +1037,8 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
     const int e = blockIdx.x, const int lane = threadIdx.x, TailObs* tl = nullptr, StepCarry* carry = nullptr,
     const void* actions_next = nullptr, void** pool_out = nullptr, const int near_ctl = 0) {
   constexpr bool kT = MODE == kTdm;
+  // Flock in the rollout translation units: the f64 polynomial constants from scalar registers
+  constexpr bool kPin = MACM_KS_PIN_FLOCK && !kT;
   static_assert(!CARRY || !kT, "the carried step is Flock's");
   static_assert(!NEARL || (!kT && NCAP == 64), "the candidate lists are the 64-record Flock sweep's");
 #ifdef MACM_TIMELINE
@@ -1084,6 +1110,7 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
   // one step of a launch to the next, so they overlay nothing
   __shared__ uint4 s_nl[NEARL ? W : 1];
   __shared__ int s_nl_state, s_nl_retry;  // s_nl_retry: the plain steps after the last failed rebuild (0: none failed)
+  __shared__ EnvCarry s_ec;  // CARRY only (as s_nl: lives across the steps of a launch)
 #ifdef MACM_STAMPS
   __shared__ int s_stat_maxisl;
   int stat_near = 0;  // kNearKind* | the largest list << 8
@@ -1234,7 +1261,7 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
       // Agent.force = _force * (1 - percent_mov_penalty * int(cooldown_mov_penalty > 0))   combat.py:46-49
       if constexpr (kT) force = P.force * (1.0 - TP.percent_mov_penalty * (double)(cdm > 0.0));
       double s0, c0, s1, c1;  // np.cos / np.sin of angle and angle + pi/2 (one reduction each)
-      act_trig(af, &s0, &c0, &s1, &c1);
+      act_trig<kPin>(af, &s0, &c0, &s1, &c1);
       const double fx = (c0 * k0 + c1 * k1) * cc * force;
       const double fy = (s0 * k0 + s1 * k1) * cc * force;
       Fx = (float)fx;  // ApplyForce: b2Vec2(float32) accumulated onto m_force = 0
@@ -1422,9 +1449,11 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
     // (The scalar DFS of T <= 64 TMW has no degree cap: it walks bit masks.)
     if (touch_over || (!fast_dfs && __builtin_amdgcn_ballot_w64(deg > DEG) != 0ull) || P.force_spill) {
       if constexpr (CARRY) {
-        // the spill step reads the state from global memory and writes it itself: the stores of the
-        // carried step before this one must have completed, and the next step loads again
-        if (carried) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        // The spill step reads the state from global memory, which a carried step has not got there
+        // (the step before stored none of it): a carried step never comes here. Its list, and with it
+        // its touching contacts, fits the register chunks, below both limits above, and force_spill
+        // holds for a whole launch, whose first step, a loading one, then ends the carry.
+        static_assert(RCH * W <= TCAP && RCH * W <= 64 * TMW, "a carried step must not need the spill step");
         carry->valid = false;
       }
       if constexpr (NEARL) s_nl_state = kNearNone;  // a spill step clears the lists
@@ -2232,26 +2261,37 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
   const unsigned long long newmask = act ? (myov & ~oldm & above) : 0ull;
   STAMP(10);
 
+  bool done_c = false;  // CARRY, wave-uniform: this step ends the episode
   if constexpr (CARRY) {
-    // Lane 0's per-env values, needed in the step's last lines only: loaded here rather than
-    // carried. Lane 0 itself stored them a step ago (a lane reads its own stores in order, no
-    // fence needed), and their registers are free during the chain and the sweep.
+    // Lane 0's per-env values live in s_ec between the steps of a launch: a carried step finds there
+    // what lane 0 left a step ago; a loading step first fills it from global memory (behind the
+    // rollout loop's fence), here and not up front, so that nothing of it is held across the chain.
+    // The step's last lines read and update them there (the time too, read again: held from here it
+    // costs the two registers that tip the 64-record float32 kernels into scratch); only whether the
+    // episode ends is needed before.
     if (lane == 0) {
-      time_passed = B.time_passed[e];
-      st_prev = B.status[e];
-      const ulonglong2* ec = reinterpret_cast<const ulonglong2*>(B.env_counters + (size_t)e * 4);
-      const ulonglong2 c01 = ec[0], c23 = ec[1];
-      ctr[0] = c01.x;
-      ctr[1] = c01.y;
-      ctr[2] = c23.x;
-      ctr[3] = c23.y;
+      if (!carried) {
+        s_ec.time_passed = B.time_passed[e];
+        s_ec.status = B.status[e];
+        // (every other writer adds atomically, in the L2: read there)
+        if (P.reward_mode == MACM_REWARD_LINEAR)
+          s_ec.rsum = __hip_atomic_load(B.env_rsum + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const ulonglong2* ec = reinterpret_cast<const ulonglong2*>(B.env_counters + (size_t)e * 4);
+        const ulonglong2 c01 = ec[0], c23 = ec[1];
+        s_ec.ctr[0] = c01.x;
+        s_ec.ctr[1] = c01.y;
+        s_ec.ctr[2] = c23.x;
+        s_ec.ctr[3] = c23.y;
+      }
     }
+    done_c = __ballot(lane == 0 && s_ec.time_passed + P.inv_hz > P.time_limit) != 0ull;
   }
   // ---- next ordered list: new pairs (desc) ++ surviving old pairs --------------
   uint32_t* ocab = B.cab[nxt] + (size_t)e * C;
   float2* ocimp = B.cimp[nxt] + (size_t)e * C;
-  // Carried step: the entries below RCH * W also go to LDS by rank, over s_tab and s_tm (both dead
-  // since the position solve), and come back lane-indexed as the next step's register chunks.
+  // Carried step: the entries below RCH * W go to LDS by rank, over s_tab and s_tm (both dead
+  // since the position solve), and come back lane-indexed as the next step's register chunks; from
+  // there they are stored to ocab / ocimp too if this step writes its state back (wb, below).
   uint32_t* const stage_ab = CARRY ? s_tab : nullptr;
   float2* const stage_im = CARRY ? reinterpret_cast<float2*>(s_tm) : nullptr;
   static_assert(sizeof(uint32_t) * RCH * W <= sizeof(s_pool.tab), "the staged entries must fit in s_tab");
@@ -2284,13 +2324,12 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
       if (w < C) {
         float2 l = make_float2(0.0f, 0.0f);
         if (touch && trank < TCAP) l = make_float2(s_tln[trank], s_tlt[trank]);
-        st_g<kState>(ocab + w, ab);
-        st_g<kState>(ocimp + w, l);
-        if constexpr (CARRY) {
-          if (w < RCH * W) {
-            stage_ab[w] = ab;
-            stage_im[w] = l;
-          }
+        if (CARRY && w < RCH * W) {  // written out with the carry's hand-over, where wb
+          stage_ab[w] = ab;
+          stage_im[w] = l;
+        } else {
+          st_g<kState>(ocab + w, ab);
+          st_g<kState>(ocimp + w, l);
         }
       }
     }
@@ -2300,6 +2339,16 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
     status |= MACM_ST_CONTACT_OVERFLOW;
     total = C;
   }
+  // This step writes the env's state back (wave-uniform). A carried step that another carried step
+  // follows does not: within a launch only this wave reads or writes the env's state rows, and the
+  // next step takes everything from StepCarry and s_ec. It does where something will read global
+  // memory: after the launch's last step (no next actions); before a step that loads (the list
+  // outgrew the register chunks, a status bit is raised, MACM_DEBUG_ROLLOUT_RELOAD: near_ctl); at an
+  // episode's end (the autoreset loop resets the env in global memory). Outputs are stored every step.
+  bool wb = true;
+  if constexpr (CARRY)
+    wb = actions_next == nullptr || (near_ctl & kStepCtlWriteBack) || total > RCH * W || done_c ||
+         __ballot(status != 0) != 0ull;
   STAMP(11);
 
   // ---- rewards (mvmnt.py:160-179) and obs (mvmnt.py:181-222) -------------------
@@ -2308,10 +2357,10 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
     if (act) {
       const float tdx = tg.x - cx, tdy = tg.y - cy;  // target - agent.body.position
       const float td2 = tdx * tdx + tdy * tdy;       // b2DistanceSquared(target, position)
-      const double d = sqrt((double)td2);
+      // binary: sqrt((double)td2) < reward_radius by its precomputed float32 threshold, no f64 sqrt
       if (coll) rew = -1.0f;
-      else if (P.reward_mode == MACM_REWARD_LINEAR) rew = (float)((-d / 35) + 1);
-      else rew = (d < P.reward_radius) ? 1.0f : 0.0f;
+      else if (P.reward_mode == MACM_REWARD_LINEAR) rew = (float)((-sqrt((double)td2) / 35) + 1);
+      else rew = (td2 < P.reward_thr2) ? 1.0f : 0.0f;
       st_g<kOut>(rew_out + ag, rew);
       if (coll_out) st_g<kOut>(coll_out + ag, (uint8_t)(coll ? 1 : 0));
       if (nbr_out) st_g<kOut>(nbr_out + ag, (int32_t)bj);
@@ -2319,14 +2368,16 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
         const int od = P.coord == MACM_COORD_CARTESIAN ? 6 : 4;
         const float2 cn = s_c[bj];
         const float rx = cn.x - cx, ry = cn.y - cy;
-        write_obs<OT>(obs + ag * od, P.coord, ang, best, rx, ry, tdx, tdy, td2);
+        write_obs<OT, kPin>(obs + ag * od, P.coord, ang, best, rx, ry, tdx, tdy, td2);
       }
       // ---- state write-back ----
-      st_g<kState>(B.pos + ag, make_float2(cx, cy));
-      st_g<kState>(B.vel + ag, make_float2(vx, vy));
-      st_g<kState>(B.angle + ag, ang);
-      st_g<kState>(B.fat + ag, fn);
-      st_g<kState>(B.sleep + ag, ns);
+      if (wb) {
+        st_g<kState>(B.pos + ag, make_float2(cx, cy));
+        st_g<kState>(B.vel + ag, make_float2(vx, vy));
+        st_g<kState>(B.angle + ag, ang);
+        st_g<kState>(B.fat + ag, fn);
+        st_g<kState>(B.sleep + ag, ns);
+      }
     }
   } else {
     // ---- TDM state write-back + TDM.get_obs (combat.py:166-167, 206-227) -------
@@ -2391,6 +2442,7 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
       }
   }
   if (lane == 0) {
+    if constexpr (CARRY) time_passed = s_ec.time_passed;
     const double tp = time_passed + P.inv_hz;  // time_passed += 1/hz
     uint8_t dn = tp > P.time_limit ? 1 : 0;
     if constexpr (kT) {
@@ -2406,26 +2458,49 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
       if (TB.winner_out) TB.winner_out[e] = win;
       TB.listener[e] = lis;
     }
-    B.time_passed[e] = tp;
-    B.done[e] = dn;
+    if constexpr (CARRY) {
+      st_prev = s_ec.status;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ctr[q] = s_ec.ctr[q];
+    }
+    if (wb) B.time_passed[e] = tp;
+    B.done[e] = dn;  // (every step: the autoreset loop reads it back)
     if (done_out) done_out[e] = dn;
-    B.step_count[e] = step_count + 1;
-    B.ccount[nxt][e] = total;
+    if (wb) {
+      B.step_count[e] = step_count + 1;
+      B.ccount[nxt][e] = total;
+    }
     const int st = (mst1 ? 1 : 0) | (mst2 ? 2 : 0) | (mst4 ? 4 : 0);
-    if (st) {
+    if (st) {  // (a step that raises a bit writes back)
       B.status[e] = st_prev | st;
       report_status(B, st);
     }
     const unsigned long long c0 = kT ? (unsigned long long)__popcll(alive0_m) : (unsigned long long)N;
-    ulonglong2* ec = reinterpret_cast<ulonglong2*>(B.env_counters + (size_t)e * 4);
-    ec[0] = make_ulonglong2(ctr[0] + c0, ctr[1] + c1);
-    ec[1] = make_ulonglong2(ctr[2] + c2, ctr[3] + (unsigned long long)dn);
-    if constexpr (!kT) {
+    if (wb) {
+      ulonglong2* ec = reinterpret_cast<ulonglong2*>(B.env_counters + (size_t)e * 4);
+      ec[0] = make_ulonglong2(ctr[0] + c0, ctr[1] + c1);
+      ec[1] = make_ulonglong2(ctr[2] + c2, ctr[3] + (unsigned long long)dn);
+    }
+    if constexpr (CARRY) {
+      // The env's reward total is its steps' sums added one by one in step order, as the atomic adds
+      // of the other steps do it: here to the running total, stored where the step writes back.
+      if (P.reward_mode == MACM_REWARD_LINEAR) {
+        const double racc = s_ec.rsum + rsum;
+        s_ec.rsum = racc;
+        if (wb) __hip_atomic_store(B.env_rsum + e, racc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      s_ec.time_passed = tp;
+      if (st) s_ec.status = st_prev | st;
+      s_ec.ctr[0] = ctr[0] + c0;
+      s_ec.ctr[1] = ctr[1] + c1;
+      s_ec.ctr[2] = ctr[2] + c2;
+      s_ec.ctr[3] = ctr[3] + (unsigned long long)dn;
+    } else if constexpr (!kT) {
       if (P.reward_mode == MACM_REWARD_LINEAR) add_reward_sum(B, e, rsum);
     }
   }
   if constexpr (CARRY) {
-    // ---- the next step's start-of-step values, from what this step stored --------
+    // ---- the next step's start-of-step values: what this step stores if it writes back ------
     // (lanes >= N: values that no lane reads, as the zeros a loading step starts them from)
     carry->p = make_float2(cx, cy);
     carry->v = make_float2(vx, vy);
@@ -2444,11 +2519,16 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
       if (k < total) {
         carry->rab[c] = stage_ab[k];
         carry->rim[c] = stage_im[k];
+        if (wb) {  // the entries that went to the stage only
+          st_g<kState>(ocab + k, carry->rab[c]);
+          st_g<kState>(ocimp + k, carry->rim[c]);
+        }
       }
     }
     // The next step must load (and this one's stores complete first: the rollout loop fences) when
     // the list has chunks beyond the register ones, which come from global memory. A step that
-    // raises a status bit ends the carry too: the launch is about to be reported as failed.
+    // raises a status bit ends the carry too: the launch is about to be reported as failed. Both
+    // are steps that wrote back (wb).
     carry->valid = total <= RCH * W && !(mst1 | mst2 | mst4);
   }
   if constexpr (NEARL) {
@@ -2773,7 +2853,8 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
     tl.k = k - A0.tail_k0;
     // the candidate lists of the nearest-neighbour sweep (near_build): Flock with 64 records
     constexpr bool kNearL = MODE == kFlock && NCAP == 64;
-    const int near_ctl = kNearL ? (k > 0 ? kNearCtlKeep : 0) | ((A.cur & kRollNearPlainBit) ? kNearCtlPlain : 0) : 0;
+    const int near_ctl = (kNearL ? (k > 0 ? kNearCtlKeep : 0) | ((A.cur & kRollNearPlainBit) ? kNearCtlPlain : 0) : 0) |
+                         (CARRY && (A.cur & kRollReloadBit) ? kStepCtlWriteBack : 0);
     if constexpr (CARRY) {
       const unsigned char* const act_k = static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride;
       step_w64_body<MODE, NCAP, OT, SCAL, true, kNearL>(

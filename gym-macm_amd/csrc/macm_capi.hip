@@ -14,6 +14,7 @@
 
 #include "flock_common.hpp"
 #include "py_mt19937.hpp"
+#include "reward_threshold.h"
 
 namespace macm {
 hipError_t launch_step_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
@@ -463,6 +464,7 @@ int macm_world_create(const macm_config* cfg, const int32_t* targets_idx, int32_
   fill_body_params(P, c.hz, c.radius, c.density, c.friction, c.linear_damping, c.agent_force,
                    c.agent_rotation_speed);
   P.reward_radius = c.reward_radius;
+  P.reward_thr2 = macm_reward_thr2(c.reward_radius);
   P.time_limit = c.time_limit;
 
   WorldBuffers& B = w->B;

@@ -13,6 +13,31 @@
 #define MACM_MATH_FN static inline
 #endif
 
+// MACM_KS(c): a polynomial constant of the functions below. The identity on the host and in every
+// device translation unit that does not define MACM_KS_SWITCH. Where one does (the rollout
+// translation units, whose step loop is built without machine LICM and so rebuilds every constant
+// each step), the functions become templates on KSPIN and, in the instantiations with KSPIN = true,
+// the constant is pinned into a scalar register pair: p = fma(p, z, C) is then a v_fma_f64 with a
+// scalar operand and two s_mov_b32, not a v_fmac_f64 that first needs C moved into its destination
+// with two v_mov_b32. The arithmetic instructions and their operands' values are the same, so
+// results are bit-identical. volatile: the pin stays where it is written, inside the step (hoisted
+// out of the step loop the constants would take some 80 scalar registers for the whole launch).
+// MACM_KS_FN(f, pin): f's instantiation (a plain f where the functions are no templates).
+#if defined(__HIPCC__) && defined(MACM_KS_SWITCH)
+template <bool KSPIN>
+__device__ __forceinline__ double macm_ks(double c) {
+  if constexpr (KSPIN) asm volatile("" : "+s"(c));
+  return c;
+}
+#define MACM_KS_TPL template <bool KSPIN = false>
+#define MACM_KS(c) macm_ks<KSPIN>(c)
+#define MACM_KS_FN(f, pin) f<pin>
+#else
+#define MACM_KS_TPL
+#define MACM_KS(c) (c)
+#define MACM_KS_FN(f, pin) f
+#endif
+
 // sin and cos of one argument, |x| < 2^19 * pi/2 (beyond that: the library, see the
 // caller). Cody-Waite reduction x = n*pi/2 + (y0 + y1) with pi/2 split into 33-bit
 // pieces p1 + p2 + p2t (fdlibm e_rem_pio2.c's constants): n*p1 and n*p2 are exact for
@@ -23,7 +48,7 @@
 // minimax kernels (k_sin.c / k_cos.c) on the double-double remainder, Horner in fma.
 // Exhaustively compared with glibc sin/cos on every float32-valued x in range and on
 // x + pi/2 (tools/trig_check.c; result in DESIGN.md §3).
-MACM_MATH_FN void macm_sincos(double x, double* sp, double* cp) {
+MACM_KS_TPL MACM_MATH_FN void macm_sincos(double x, double* sp, double* cp) {
   const double fn = rint(x * 6.36619772367581382433e-01);  // round(x * 2/pi)
   const int q = (int)fn;
   const double t1 = fma(-fn, 1.57079632673412561417e+00, x);  // exact
@@ -35,20 +60,20 @@ MACM_MATH_FN void macm_sincos(double x, double* sp, double* cp) {
   const double y1 = (r2 - y0) + tail;
   const double z = y0 * y0;
   // k_sin: sin(y0 + y1) = y0 + (y0^3 S(z) + y1 (1 - z/2) ...)
-  double ps = 1.58969099521155010221e-10;
-  ps = fma(ps, z, -2.50507602534068634195e-08);
-  ps = fma(ps, z, 2.75573137070700676789e-06);
-  ps = fma(ps, z, -1.98412698298579493134e-04);
-  ps = fma(ps, z, 8.33333333332248946124e-03);
+  double ps = MACM_KS(1.58969099521155010221e-10);
+  ps = fma(ps, z, MACM_KS(-2.50507602534068634195e-08));
+  ps = fma(ps, z, MACM_KS(2.75573137070700676789e-06));
+  ps = fma(ps, z, MACM_KS(-1.98412698298579493134e-04));
+  ps = fma(ps, z, MACM_KS(8.33333333332248946124e-03));
   const double v = z * y0;
-  const double s = y0 - ((z * (0.5 * y1 - v * ps) - y1) - v * -1.66666666666666324348e-01);
+  const double s = y0 - ((z * (0.5 * y1 - v * ps) - y1) - v * MACM_KS(-1.66666666666666324348e-01));
   // k_cos: cos(y0 + y1) = 1 - z/2 + z^2 C(z) - y0*y1, with the 1 - z/2 split exact
-  double pc = -1.13596475577881948265e-11;
-  pc = fma(pc, z, 2.08757232129817482790e-09);
-  pc = fma(pc, z, -2.75573143513906633035e-07);
-  pc = fma(pc, z, 2.48015872894767294178e-05);
-  pc = fma(pc, z, -1.38888888888741095749e-03);
-  pc = fma(pc, z, 4.16666666666666019037e-02);
+  double pc = MACM_KS(-1.13596475577881948265e-11);
+  pc = fma(pc, z, MACM_KS(2.08757232129817482790e-09));
+  pc = fma(pc, z, MACM_KS(-2.75573143513906633035e-07));
+  pc = fma(pc, z, MACM_KS(2.48015872894767294178e-05));
+  pc = fma(pc, z, MACM_KS(-1.38888888888741095749e-03));
+  pc = fma(pc, z, MACM_KS(4.16666666666666019037e-02));
   const double hz = 0.5 * z;
   const double wc = 1.0 - hz;
   const double c = wc + (((1.0 - wc) - hz) + (z * (z * pc) - y0 * y1));
@@ -68,7 +93,7 @@ MACM_MATH_FN void macm_sincos(double x, double* sp, double* cp) {
 // kernels like y1; |err| <= ulp(x1)/2, so this is only accurate for small |x| (|x| < 4:
 // |y1'| < 2^-51; see macm_action_trig_raw). Its quadrant is q + 1. The kernels are then
 // finished twice: ~30 f64 ops instead of a second full evaluation.
-MACM_MATH_FN void macm_sincos_pair(double x, double* s0p, double* c0p, double* s1p, double* c1p) {
+MACM_KS_TPL MACM_MATH_FN void macm_sincos_pair(double x, double* s0p, double* c0p, double* s1p, double* c1p) {
   const double fn = rint(x * 6.36619772367581382433e-01);  // round(x * 2/pi)
   const int q = (int)fn;
   const double t1 = fma(-fn, 1.57079632673412561417e+00, x);  // exact
@@ -85,22 +110,22 @@ MACM_MATH_FN void macm_sincos_pair(double x, double* s0p, double* c0p, double* s
   const double err = (x - (x1 - bp)) + (P - bp);
   const double y1b = y1 - (6.12323399573676603587e-17 + err);
   const double z = y0 * y0;
-  double ps = 1.58969099521155010221e-10;
-  ps = fma(ps, z, -2.50507602534068634195e-08);
-  ps = fma(ps, z, 2.75573137070700676789e-06);
-  ps = fma(ps, z, -1.98412698298579493134e-04);
-  ps = fma(ps, z, 8.33333333332248946124e-03);
+  double ps = MACM_KS(1.58969099521155010221e-10);
+  ps = fma(ps, z, MACM_KS(-2.50507602534068634195e-08));
+  ps = fma(ps, z, MACM_KS(2.75573137070700676789e-06));
+  ps = fma(ps, z, MACM_KS(-1.98412698298579493134e-04));
+  ps = fma(ps, z, MACM_KS(8.33333333332248946124e-03));
   const double v = z * y0;
-  const double vs = v * -1.66666666666666324348e-01;
+  const double vs = v * MACM_KS(-1.66666666666666324348e-01);
   const double vps = v * ps;
   const double sa = y0 - ((z * (0.5 * y1 - vps) - y1) - vs);
   const double sb = y0 - ((z * (0.5 * y1b - vps) - y1b) - vs);
-  double pc = -1.13596475577881948265e-11;
-  pc = fma(pc, z, 2.08757232129817482790e-09);
-  pc = fma(pc, z, -2.75573143513906633035e-07);
-  pc = fma(pc, z, 2.48015872894767294178e-05);
-  pc = fma(pc, z, -1.38888888888741095749e-03);
-  pc = fma(pc, z, 4.16666666666666019037e-02);
+  double pc = MACM_KS(-1.13596475577881948265e-11);
+  pc = fma(pc, z, MACM_KS(2.08757232129817482790e-09));
+  pc = fma(pc, z, MACM_KS(-2.75573143513906633035e-07));
+  pc = fma(pc, z, MACM_KS(2.48015872894767294178e-05));
+  pc = fma(pc, z, MACM_KS(-1.38888888888741095749e-03));
+  pc = fma(pc, z, MACM_KS(4.16666666666666019037e-02));
   const double hz = 0.5 * z;
   const double wc = 1.0 - hz;
   const double cz = ((1.0 - wc) - hz) + z * (z * pc);
@@ -141,17 +166,17 @@ MACM_MATH_FN void macm_sincos_pair(double x, double* s0p, double* c0p, double* s
 // x + pi/2 as a first-order correction, which is accurate only while that error is far
 // below ulp(y0): |x| < 4 covers every angle the step produces (it wraps into [-pi, pi]);
 // larger angles (injected state) take two independent reductions.
-MACM_MATH_FN void macm_action_trig_raw(double x, double* s0, double* c0, double* s1, double* c1) {
+MACM_KS_TPL MACM_MATH_FN void macm_action_trig_raw(double x, double* s0, double* c0, double* s1, double* c1) {
   if (fabs(x) < 4.0) {
-    macm_sincos_pair(x, s0, c0, s1, c1);
+    MACM_KS_FN(macm_sincos_pair, KSPIN)(x, s0, c0, s1, c1);
   } else {
-    macm_sincos(x, s0, c0);
-    macm_sincos(x + M_PI / 2, s1, c1);
+    MACM_KS_FN(macm_sincos, KSPIN)(x, s0, c0);
+    MACM_KS_FN(macm_sincos, KSPIN)(x + M_PI / 2, s1, c1);
   }
 }
 
-MACM_MATH_FN void macm_action_trig(float a, double* s0, double* c0, double* s1, double* c1) {
-  macm_action_trig_raw((double)a, s0, c0, s1, c1);
+MACM_KS_TPL MACM_MATH_FN void macm_action_trig(float a, double* s0, double* c0, double* s1, double* c1) {
+  MACM_KS_FN(macm_action_trig_raw, KSPIN)((double)a, s0, c0, s1, c1);
   int hit = 0;
   for (int i = 0; i < MACM_TRIG_NNEAR; ++i) hit |= a == (float)kTrigFixNear[i][0];
   if (hit) {
@@ -181,7 +206,7 @@ MACM_MATH_FN void macm_action_trig(float a, double* s0, double* c0, double* s1, 
 // Split in two so that the pair (y, x) / (-y, -x) seen from both agents of a TDM pair shares
 // the reduction and polynomial: obs_atan2_core depends on |x|, |y| only; obs_atan2_finish
 // applies the quadrant from the signs. obs_atan2(y, x) is exactly finish(core(|x|, |y|), y, x).
-MACM_MATH_FN double obs_atan2_core(double ax, double ay) {
+MACM_KS_TPL MACM_MATH_FN double obs_atan2_core(double ax, double ay) {
   const int swap = ay > ax;
   const double mx = swap ? ay : ax, mn = swap ? ax : ay;
   const int r0 = mn < 0.4375 * mx;         // id -1: atan(a) directly
@@ -189,17 +214,17 @@ MACM_MATH_FN double obs_atan2_core(double ax, double ay) {
   const double ca = r1 ? 2.0 : 1.0, cb = r0 ? 0.0 : 1.0, cd = r0 ? 0.0 : 1.0;
   const double xr = fma(ca, mn, -(cb * mx)) / fma(cd, mn, ca * mx);
   const double z = xr * xr;
-  double p = 1.62858201153657823623e-02;
-  p = fma(p, z, -3.65315727442169155270e-02);
-  p = fma(p, z, 4.97687799461593236017e-02);
-  p = fma(p, z, -5.83357013379057348645e-02);
-  p = fma(p, z, 6.66107313738753120669e-02);
-  p = fma(p, z, -7.69187620504482999495e-02);
-  p = fma(p, z, 9.09088713343650656196e-02);
-  p = fma(p, z, -1.11111104054623557880e-01);
-  p = fma(p, z, 1.42857142725034663711e-01);
-  p = fma(p, z, -1.99999999998764832476e-01);
-  p = fma(p, z, 3.33333333333329318027e-01);
+  double p = MACM_KS(1.62858201153657823623e-02);
+  p = fma(p, z, MACM_KS(-3.65315727442169155270e-02));
+  p = fma(p, z, MACM_KS(4.97687799461593236017e-02));
+  p = fma(p, z, MACM_KS(-5.83357013379057348645e-02));
+  p = fma(p, z, MACM_KS(6.66107313738753120669e-02));
+  p = fma(p, z, MACM_KS(-7.69187620504482999495e-02));
+  p = fma(p, z, MACM_KS(9.09088713343650656196e-02));
+  p = fma(p, z, MACM_KS(-1.11111104054623557880e-01));
+  p = fma(p, z, MACM_KS(1.42857142725034663711e-01));
+  p = fma(p, z, MACM_KS(-1.99999999998764832476e-01));
+  p = fma(p, z, MACM_KS(3.33333333333329318027e-01));
   const double sz = z * p;
   const double hi = r1 ? 4.63647609000806093515e-01 : 7.85398163397448278999e-01;
   const double lo = r1 ? 2.26987774529616870924e-17 : 3.06161699786838301793e-17;
@@ -214,4 +239,6 @@ MACM_MATH_FN double obs_atan2_finish(double r, double y, double x) {
   return copysign(r, y);
 }
 
-MACM_MATH_FN double obs_atan2(double y, double x) { return obs_atan2_finish(obs_atan2_core(fabs(x), fabs(y)), y, x); }
+MACM_KS_TPL MACM_MATH_FN double obs_atan2(double y, double x) {
+  return obs_atan2_finish(MACM_KS_FN(obs_atan2_core, KSPIN)(fabs(x), fabs(y)), y, x);
+}

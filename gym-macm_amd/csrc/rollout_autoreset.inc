@@ -178,7 +178,8 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
     int sl = (int)threadIdx.x;
     if constexpr (MODE == kTdm) asm volatile("" : "+v"(sl));
     void* lds = nullptr;  // the step's contact pool, dead once the step ends
-    const int near_ctl = kNearL ? near_keep | ((A.cur & kRollNearPlainBit) ? kNearCtlPlain : 0) : 0;
+    const int near_ctl = (kNearL ? near_keep | ((A.cur & kRollNearPlainBit) ? kNearCtlPlain : 0) : 0) |
+                         (CARRY && (A.cur & kRollReloadBit) ? kStepCtlWriteBack : 0);
     if constexpr (CARRY) {
       const unsigned char* const act_k = static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride;
       step_w64_body<MODE, NCAP, OT, SCAL, true, kNearL>(
