@@ -117,4 +117,49 @@ hipError_t launch_draw_poses(const uint8_t* mask, uint32_t* mt, const PoseDraw& 
   return hipGetLastError();
 }
 
+// The per-step autoreset's copy into the registered final outputs (macm_*_set_final_outputs), between
+// the private copy of the step's done flags (mask) and the draw and init launches that overwrite the
+// output row and clear step_count: one block per env, the envs that did not end return at once. obs /
+// nbr / msk: the step's output rows ([E, ...]; row k of a trajectory); obs_bytes, n_nbr, n_msk: per env.
+// An env's obs row is a whole number of 16-byte vectors, aligned, except a float32 cartesian Flock row
+// of an odd N (24 N bytes): that one goes by words.
+__global__ __launch_bounds__(256) void final_copy_kernel(const uint8_t* __restrict__ mask, FinalOut F,
+                                                         const unsigned char* __restrict__ obs,
+                                                         const int32_t* __restrict__ nbr,
+                                                         const uint8_t* __restrict__ msk,
+                                                         const int32_t* __restrict__ step_count,
+                                                         unsigned long long obs_bytes, int n_nbr, int n_msk) {
+  const int e = blockIdx.x;
+  if (!mask[e]) return;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  if (F.obs) {
+    const unsigned char* const src = obs + (size_t)e * obs_bytes;
+    unsigned char* const dst = static_cast<unsigned char*>(F.obs) + (size_t)e * obs_bytes;
+    if ((obs_bytes & 15ull) == 0ull) {
+      const size_t nv = obs_bytes / 16;
+      for (size_t v = tid; v < nv; v += nt) reinterpret_cast<uint4*>(dst)[v] = reinterpret_cast<const uint4*>(src)[v];
+    } else {
+      const size_t nw = obs_bytes / 4;
+      for (size_t v = tid; v < nw; v += nt)
+        reinterpret_cast<uint32_t*>(dst)[v] = reinterpret_cast<const uint32_t*>(src)[v];
+    }
+  }
+  if (F.nbr_id)
+    for (int i = tid; i < n_nbr; i += nt) F.nbr_id[(size_t)e * n_nbr + i] = nbr[(size_t)e * n_nbr + i];
+  if (F.mask)
+    for (int i = tid; i < n_msk; i += nt) F.mask[(size_t)e * n_msk + i] = msk[(size_t)e * n_msk + i];
+  if (tid == 0) {
+    if (F.length) F.length[e] = step_count[e];
+    if (F.ends) F.ends[e] += 1;
+  }
+}
+
+hipError_t launch_final_copy(const uint8_t* mask, const FinalOut& F, const void* obs, const int32_t* nbr,
+                             const uint8_t* msk, const int32_t* step_count, unsigned long long obs_bytes, int n_nbr,
+                             int n_msk, int n_envs, hipStream_t s) {
+  hipLaunchKernelGGL(final_copy_kernel, dim3(n_envs), dim3(256), 0, s, mask, F, static_cast<const unsigned char*>(obs),
+                     nbr, msk, step_count, obs_bytes, n_nbr, n_msk);
+  return hipGetLastError();
+}
+
 }  // namespace macm

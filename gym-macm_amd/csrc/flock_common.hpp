@@ -461,4 +461,15 @@ struct PoseDraw {
   TdmParams TP;                     // TDM team boundaries
 };
 
+// macm_final_outputs as the kernels take it (macm_*_set_final_outputs): per-env rows that keep what an
+// autoreset would overwrite in the step's output row. All NULL: nothing registered.
+struct FinalOut {
+  void* obs;        // Flock [E, N, OD], TDM [E, N, N-1, 4], the world's obs type
+  int32_t* nbr_id;  // Flock [E, N]
+  uint8_t* mask;    // TDM [E, N, N-1]
+  int32_t* length;  // [E]
+  int32_t* ends;    // [E]
+  __host__ __device__ bool any() const { return obs || nbr_id || mask || length || ends; }
+};
+
 }  // namespace macm

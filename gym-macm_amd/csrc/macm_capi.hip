@@ -46,16 +46,19 @@ int tdm_rollout_resident_blocks(int n_agents, bool obs_f64);
 hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
                                  bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
                                  int nsteps, unsigned long long astride, int traj, int reload, uint32_t* mt,
-                                 const PoseDraw& D);
+                                 const PoseDraw& D, const FinalOut& F);
 hipError_t launch_tdm_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                      const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
                                      uint8_t* done, hipStream_t s, int nsteps, unsigned long long astride, int traj,
-                                     uint32_t* mt, const PoseDraw& D);
+                                     uint32_t* mt, const PoseDraw& D, const FinalOut& F);
 hipError_t launch_tdm_init_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                const TdmBuffers& TB, int cur, void* obs, bool obs_f64, const uint8_t* mask,
                                hipStream_t s);
 hipError_t launch_draw_poses(const uint8_t* mask, uint32_t* mt, const PoseDraw& D, int n_envs, float2* pos,
                              float* angle, hipStream_t s);
+hipError_t launch_final_copy(const uint8_t* mask, const FinalOut& F, const void* obs, const int32_t* nbr,
+                             const uint8_t* msk, const int32_t* step_count, unsigned long long obs_bytes, int n_nbr,
+                             int n_msk, int n_envs, hipStream_t s);
 hipError_t launch_tdm_step_wg(const StepParams& P, const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB,
                               int cur, const void* actions, void* obs, bool obs_f64, uint8_t* done, hipStream_t s);
 hipError_t launch_tdm_init_wg(const StepParams& P, const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB,
@@ -108,6 +111,7 @@ struct macm_world {
   uint8_t* rmask = nullptr;   // [E] reset mask scratch
   bool mt_valid = false;
   bool autoreset = false;     // macm_world_set_autoreset: step and rollouts restart the envs that end
+  FinalOut fin{};             // macm_world_set_final_outputs: the caller's buffers, kept until replaced or cleared
   uint32_t* hstat = nullptr;  // host-mapped status word (B.host_status is its device alias)
   unsigned long long* bad = nullptr;  // validate_actions: first failing row (device scratch)
   // workgroup-path rollouts: env slices on streams of their own (created on first use)
@@ -137,6 +141,7 @@ struct macm_tdm {
   uint8_t* rmask = nullptr;
   bool mt_valid = false;
   bool autoreset = false;  // macm_tdm_set_autoreset
+  FinalOut fin{};          // macm_tdm_set_final_outputs
   uint32_t* hstat = nullptr;
   unsigned long long* bad = nullptr;
   int slots_alloc = 0;  // as macm_world
@@ -686,9 +691,53 @@ int macm_world_set_autoreset(macm_world* w, int32_t on) {
 // the step's done flags, as a private copy (the init kernel clears B.done; the output row keeps its
 // 1), mask the draw and init launches. All on the stream, no host round trip; the host-mapped
 // status word is not resynced here.
+// With final outputs registered, the rows the init is about to overwrite are copied out first
+// (final_copy_kernel, the same mask), launched only then.
 static int world_autoreset_step(macm_world* w, const macm_outputs* out, hipStream_t s) {
   HIP_TRY(hipMemcpyAsync(w->rmask, w->B.done, (size_t)w->P.n_envs, hipMemcpyDeviceToDevice, s));
+  if (w->fin.any()) {
+    const unsigned long long obytes =
+        (unsigned long long)w->P.n_agents * obs_dim(w->cfg) * (w->cfg.obs_f64 ? sizeof(double) : sizeof(float));
+    HIP_TRY(launch_final_copy(w->rmask, w->fin, out->obs, out->nbr_id, nullptr, w->B.step_count, obytes, w->P.n_agents,
+                              0, w->P.n_envs, s));
+  }
   return world_reset_masked(w, out, s);
+}
+
+// The caller's final outputs as the kernels take them; `mask` / `nbr_id` as the env kind ignores them.
+static int final_outputs_from(const macm_final_outputs* fin, bool tdm, FinalOut* F) {
+  *F = FinalOut{};
+  if (!fin) return MACM_OK;
+  if (reinterpret_cast<uintptr_t>(fin->obs) & 15)
+    return fail(MACM_E_INVALID, "final outputs: obs must be 16-byte aligned");
+  F->obs = fin->obs;
+  F->nbr_id = tdm ? nullptr : fin->nbr_id;
+  F->mask = tdm ? fin->mask : nullptr;
+  F->length = fin->length;
+  F->ends = fin->ends;
+  return MACM_OK;
+}
+
+// An autoreset call copies a final row from the call's own output row: that row must exist. Checked
+// before anything is launched.
+static int final_outputs_need(bool autoreset, const FinalOut& F, const void* obs, const void* nbr_id,
+                              const void* mask) {
+  if (!autoreset) return MACM_OK;
+  if (F.obs && !obs) return fail(MACM_E_INVALID, "final outputs: obs is registered, so the call's obs output must be set");
+  if (F.nbr_id && !nbr_id)
+    return fail(MACM_E_INVALID, "final outputs: nbr_id is registered, so the call's nbr_id output must be set");
+  if (F.mask && !mask)
+    return fail(MACM_E_INVALID, "final outputs: mask is registered, so the call's mask output must be set");
+  return MACM_OK;
+}
+
+int macm_world_set_final_outputs(macm_world* w, const macm_final_outputs* fin) {
+  if (!w) return fail(MACM_E_INVALID, "world is NULL");
+  FinalOut F;
+  const int rc = final_outputs_from(fin, false, &F);
+  if (rc) return rc;
+  w->fin = F;
+  return MACM_OK;
 }
 
 static int overflow_error(uint32_t st) {
@@ -736,6 +785,7 @@ static HandoffStream* handoff_for(macm_world* w) {
 int macm_world_step(macm_world* w, const void* actions, const macm_outputs* out, void* stream) {
   if (!w || !actions || !out || !out->reward) return fail(MACM_E_INVALID, "world/actions/out/reward is NULL");
   if (w->autoreset && !w->mt_valid) return fail(MACM_E_INVALID, kNoStreams);
+  if (const int rc = final_outputs_need(w->autoreset, w->fin, out->obs, out->nbr_id, nullptr)) return rc;
   if (const uint32_t st = read_host_status(w->hstat)) return overflow_error(st);
   DeviceGuard g(w->device);
   if (w->cfg.validate_actions) {
@@ -892,6 +942,7 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
   if (bots && !out->obs) return fail(MACM_E_INVALID, "out->obs is NULL (the bots act on it)");
   if (bots && w->cfg.action_mode != MACM_ACTION_DISCRETE) return fail(MACM_E_INVALID, "bots.flock acts in discrete mode");
   if (w->autoreset && !w->mt_valid) return fail(MACM_E_INVALID, kNoStreams);
+  if (const int rc = final_outputs_need(w->autoreset, w->fin, out->obs, out->nbr_id, nullptr)) return rc;
   if (const uint32_t st = read_host_status(w->hstat)) return overflow_error(st);
   DeviceGuard g(w->device);
   hipStream_t s = (hipStream_t)stream;
@@ -909,7 +960,7 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
     if (w->autoreset)  // the kernels with the in-launch reset
       HIP_TRY(launch_rollout_ar_w64(w->P, w->B, w->cur, actions, out->obs, w->cfg.obs_f64 != 0, out->nbr_id,
                                     out->reward, out->collided, out->done, s, n_steps, astride, traj ? 1 : 0,
-                                    w->roll_reload, w->mt, world_pose_draw(w)));
+                                    w->roll_reload, w->mt, world_pose_draw(w), w->fin));
     else
       HIP_TRY(launch_rollout_w64(w->P, w->B, w->cur, actions, out->obs, w->cfg.obs_f64 != 0, out->nbr_id, out->reward,
                                  out->collided, out->done, s, n_steps, astride, traj ? 1 : 0, w->roll_reload));
@@ -1508,11 +1559,25 @@ int macm_tdm_set_autoreset(macm_tdm* w, int32_t on) {
   return MACM_OK;
 }
 
+int macm_tdm_set_final_outputs(macm_tdm* w, const macm_final_outputs* fin) {
+  if (!w) return fail(MACM_E_INVALID, "tdm is NULL");
+  FinalOut F;
+  const int rc = final_outputs_from(fin, true, &F);
+  if (rc) return rc;
+  w->fin = F;
+  return MACM_OK;
+}
+
 // As world_autoreset_step: the step's done flags (a private copy) mask the draw and init launches.
 // TB / obs: the step's outputs; the init writes the new initial obs and mask there and leaves the
 // terminal health, alive and winner outputs as the step wrote them.
 static int tdm_autoreset_step(macm_tdm* w, const TdmBuffers& TB, void* obs, hipStream_t s) {
   HIP_TRY(hipMemcpyAsync(w->rmask, w->B.done, (size_t)w->P.n_envs, hipMemcpyDeviceToDevice, s));
+  if (w->fin.any()) {  // the rows the init overwrites, into the registered final outputs first
+    const size_t S = (size_t)w->P.n_agents * (w->P.n_agents - 1);
+    HIP_TRY(launch_final_copy(w->rmask, w->fin, obs, nullptr, TB.mask_out, w->B.step_count,
+                              S * 4 * (w->cfg.obs_f64 ? sizeof(double) : sizeof(float)), 0, (int)S, w->P.n_envs, s));
+  }
   HIP_TRY(launch_draw_poses(w->rmask, w->mt, tdm_pose_draw(w), w->P.n_envs, w->B.pos, w->B.angle, s));
   TdmBuffers TBi = TB;
   TBi.health_out = nullptr;
@@ -1578,6 +1643,9 @@ static int tdm_split_buffers(macm_tdm* w, size_t rows, hipStream_t s) {
 int macm_tdm_step(macm_tdm* w, const void* actions, const macm_tdm_outputs* out, void* stream) {
   if (!w || !actions) return fail(MACM_E_INVALID, "tdm/actions is NULL");
   if (w->autoreset && !w->mt_valid) return fail(MACM_E_INVALID, kNoTdmStreams);
+  if (const int rc = final_outputs_need(w->autoreset, w->fin, out ? out->obs : nullptr, nullptr,
+                                        out ? out->mask : nullptr))
+    return rc;
   if (const uint32_t st = read_host_status(w->hstat)) return overflow_error(st);
   DeviceGuard g(w->device);
   if (w->cfg.validate_actions) {
@@ -1744,6 +1812,9 @@ static int tdm_rollout(macm_tdm* w, const void* actions, int n_steps, const macm
   if ((bots || traj) && !out) return fail(MACM_E_INVALID, "out is NULL");
   if (bots && (!out->obs || !out->mask)) return fail(MACM_E_INVALID, "out->obs/mask is NULL (the bots act on them)");
   if (w->autoreset && !w->mt_valid) return fail(MACM_E_INVALID, kNoTdmStreams);
+  if (const int rc = final_outputs_need(w->autoreset, w->fin, out ? out->obs : nullptr, nullptr,
+                                        out ? out->mask : nullptr))
+    return rc;
   if (const uint32_t st = read_host_status(w->hstat)) return overflow_error(st);
   DeviceGuard g(w->device);
   hipStream_t s = (hipStream_t)stream;
@@ -1795,7 +1866,7 @@ static int tdm_rollout(macm_tdm* w, const void* actions, int n_steps, const macm
   if (w->autoreset)  // the kernels with the in-launch reset (the observation inside the step)
     HIP_TRY(launch_tdm_rollout_ar_w64(w->P, w->B, w->TP, TB, w->cur, actions, out ? out->obs : nullptr,
                                       w->cfg.obs_f64 != 0, out ? out->done : nullptr, s, n_steps, astride, traj ? 1 : 0,
-                                      w->mt, tdm_pose_draw(w)));
+                                      w->mt, tdm_pose_draw(w), w->fin));
   else
     HIP_TRY(launch_tdm_rollout_w64(w->P, w->B, w->TP, TB, w->cur, actions, out ? out->obs : nullptr,
                                    w->cfg.obs_f64 != 0, out ? out->done : nullptr, s, n_steps, astride, traj ? 1 : 0));

@@ -134,11 +134,59 @@ __device__ __forceinline__ void reset_env_w64(const StepParams& P, const WorldBu
   }
 }
 
+// What the reset is about to overwrite, kept in the env's row of the registered final outputs
+// (macm_*_set_final_outputs), by the env's own wave behind the fence that follows the step: obs /
+// nbr_out / mask_out are step k's output rows as the step stored them. Flock: lane = agent copies the
+// row it stored itself (a float32 polar row is one 16-byte vector). TDM: the env's N (N - 1) slots are
+// contiguous and 16-byte aligned, copied lane-strided as 16-byte vectors (a float64 slot: two); its
+// N (N - 1) mask bytes by bytes (20 * 19 = 380: a mask row is not 16-byte aligned in general).
+// length is the step count the step wrote back (an episode-ending step always does: wb), by the lane
+// that stored it. Nothing registered: one wave-uniform test.
+template <int MODE, typename OT>
+__device__ __forceinline__ void final_copy_w64(const FinalOut& F, const WorldBuffers& B, int N, int od,
+                                               const OT* __restrict__ obs, const int32_t* __restrict__ nbr_out,
+                                               const uint8_t* __restrict__ mask_out, int e, int lane) {
+  if (!F.any()) return;
+  if constexpr (MODE == kFlock) {
+    if (lane < N) {
+      const size_t ag = (size_t)e * N + lane;
+      if (F.obs) {
+        OT* const dst = static_cast<OT*>(F.obs) + ag * od;
+        const OT* const src = obs + ag * od;
+        if (sizeof(OT) == 4 && od == 4) {
+          *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
+        } else {
+          for (int q = 0; q < od; ++q) dst[q] = src[q];
+        }
+      }
+      if (F.nbr_id) F.nbr_id[ag] = nbr_out[ag];
+    }
+  } else {
+    const size_t S = (size_t)N * (N - 1);  // the env's slots
+    if (F.obs) {
+      const size_t nv = S * (sizeof(OT) / 4);  // 16-byte vectors
+      const uint4* const src = reinterpret_cast<const uint4*>(obs + (size_t)e * S * 4);
+      uint4* const dst = reinterpret_cast<uint4*>(static_cast<OT*>(F.obs) + (size_t)e * S * 4);
+      for (size_t v = lane; v < nv; v += W) dst[v] = src[v];
+    }
+    if (F.mask) {
+      const uint8_t* const src = mask_out + (size_t)e * S;
+      uint8_t* const dst = F.mask + (size_t)e * S;
+      for (size_t b = lane; b < S; b += W) dst[b] = src[b];
+    }
+  }
+  if (lane == 0) {
+    if (F.length) F.length[e] = B.step_count[e];
+    if (F.ends) F.ends[e] += 1;
+  }
+}
+
 template <typename OT>
 struct RolloutArArgs {  // the kernel's only argument (kernarg offset 0)
   RolloutArgs<OT> A;
   uint32_t* mt;  // [E][kMtStride] the envs' streams
   PoseDraw D;
+  FinalOut F;  // last: the fields before it keep their offsets
 };
 
 // env_rollout_w64 with the in-launch reset; no tail or split observation (their pose snapshots know
@@ -211,7 +259,9 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
     }
     __syncthreads();
     if (dn) {
-      // behind the fence: the reset's stores follow the step's to the same rows (state, list, obs)
+      // behind the fence: the reset's stores follow the step's to the same rows (state, list, obs);
+      // before them, the rows they overwrite go to the registered final outputs
+      final_copy_w64<MODE, OT>(R.F, A.B, N, (int)od, obs, nbr, TB.mask_out, env, rl);
       reset_env_w64<MODE, OT>(A.P, A.B, A.TP, TB, R.D, R.mt, (A.cur ^ (k + 1)) & 1, obs, nbr, env, rl, lds);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __syncthreads();
@@ -239,7 +289,7 @@ template <int MODE, int NCAP, typename OT, bool SCAL = false>
 static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hipStream_t s, const StepParams& P,
                            const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur, const void* actions,
                            void* obs, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, int reload, uint32_t* mt,
-                           const PoseDraw& D) {
+                           const PoseDraw& D, const FinalOut& F) {
   // astride == 0: closed loop, `actions` is the bots' action buffer
   uint8_t* pol = astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(actions)) : nullptr;
   if (B.sched && nsteps >= kRollBalanceMinSteps) {  // the balanced env order, as launch_roll
@@ -250,7 +300,8 @@ static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hip
   RolloutArArgs<OT> R{{P, B, TP, TB, actions, (OT*)obs, nbr, rew, coll, done, astride, cur, nsteps, pol, traj, 0, nullptr,
                        0u, 0},
                       mt,
-                      D};
+                      D,
+                      F};
   if constexpr (MODE == kFlock) {
     if (!pol) {  // actions given: the carried step
       if (reload & 1) R.A.cur |= kRollReloadBit;
@@ -267,27 +318,27 @@ static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hip
 hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
                                  bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
                                  int nsteps, unsigned long long astride, int traj, int reload, uint32_t* mt,
-                                 const PoseDraw& D) {
+                                 const PoseDraw& D, const FinalOut& F) {
   const TdmParams TP{};
   const TdmBuffers TB{};
   const bool small = P.n_agents <= 32;
   if (obs_f64) {
     if (small)
       launch_roll_ar<kFlock, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                        reload, mt, D);
+                                        reload, mt, D, F);
     else
       launch_roll_ar<kFlock, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                        reload, mt, D);
+                                        reload, mt, D, F);
   } else {
     if (small)
       launch_roll_ar<kFlock, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                       reload, mt, D);
+                                       reload, mt, D, F);
     else if (P.n_envs >= kScalarSweepMinEnvs)
       launch_roll_ar<kFlock, 64, float, true>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll,
-                                             done, reload, mt, D);
+                                             done, reload, mt, D, F);
     else
       launch_roll_ar<kFlock, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                       reload, mt, D);
+                                       reload, mt, D, F);
   }
   return hipGetLastError();
 }
@@ -295,22 +346,22 @@ hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int
 hipError_t launch_tdm_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                      const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
                                      uint8_t* done, hipStream_t s, int nsteps, unsigned long long astride, int traj,
-                                     uint32_t* mt, const PoseDraw& D) {
+                                     uint32_t* mt, const PoseDraw& D, const FinalOut& F) {
   const bool small = P.n_agents <= 32;
   if (obs_f64) {
     if (small)
       launch_roll_ar<kTdm, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                      nullptr, done, 0, mt, D);
+                                      nullptr, done, 0, mt, D, F);
     else
       launch_roll_ar<kTdm, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                      nullptr, done, 0, mt, D);
+                                      nullptr, done, 0, mt, D, F);
   } else {
     if (small)
       launch_roll_ar<kTdm, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                     nullptr, done, 0, mt, D);
+                                     nullptr, done, 0, mt, D, F);
     else
       launch_roll_ar<kTdm, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                     nullptr, done, 0, mt, D);
+                                     nullptr, done, 0, mt, D, F);
   }
   return hipGetLastError();
 }

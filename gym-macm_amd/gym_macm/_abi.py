@@ -72,6 +72,11 @@ class MacmOutputs(Structure):
     ]
 
 
+class MacmFinalOutputs(Structure):
+    """macm_final_outputs: where an autoreset world keeps what the reset overwrites (None = not wanted)."""
+    _fields_ = [(n, c_void_p) for n in ("obs", "nbr_id", "mask", "length", "ends")]
+
+
 class MacmState(Structure):
     _fields_ = [(n, c_void_p) for n in (
         "pos", "vel", "angle", "fat", "sleep", "targets", "contact_count", "contact_ab",
@@ -202,6 +207,7 @@ SIGNATURES = {
     "macm_world_place": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(MacmOutputs), c_void_p]),
     "macm_world_reset_envs": (c_int, [c_void_p, c_void_p, POINTER(MacmOutputs), c_void_p]),
     "macm_world_set_autoreset": (c_int, [c_void_p, c_int32]),
+    "macm_world_set_final_outputs": (c_int, [c_void_p, POINTER(MacmFinalOutputs)]),
     "macm_world_step": (c_int, [c_void_p, c_void_p, POINTER(MacmOutputs), c_void_p]),
     "macm_world_rollout": (c_int, [c_void_p, c_void_p, c_int, POINTER(MacmOutputs), c_void_p]),
     "macm_world_rollout_bots": (c_int, [c_void_p, c_void_p, c_int, POINTER(MacmOutputs), c_void_p]),
@@ -223,6 +229,7 @@ SIGNATURES = {
     "macm_tdm_place": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(MacmTdmOutputs), c_void_p]),
     "macm_tdm_reset_envs": (c_int, [c_void_p, c_void_p, POINTER(MacmTdmOutputs), c_void_p]),
     "macm_tdm_set_autoreset": (c_int, [c_void_p, c_int32]),
+    "macm_tdm_set_final_outputs": (c_int, [c_void_p, POINTER(MacmFinalOutputs)]),
     "macm_tdm_step": (c_int, [c_void_p, c_void_p, POINTER(MacmTdmOutputs), c_void_p]),
     "macm_tdm_rollout": (c_int, [c_void_p, c_void_p, c_int, POINTER(MacmTdmOutputs), c_void_p]),
     "macm_tdm_rollout_bots": (c_int, [c_void_p, c_void_p, c_int, POINTER(MacmTdmOutputs), c_void_p]),

@@ -45,7 +45,7 @@ class TdmWorld:
     owned by this object and overwritten by every call."""
 
     def __init__(self, cfg: _abi.MacmTdmConfig, n_envs: int = 1, device=None, host_outputs: bool = False,
-                 autoreset: bool = False):
+                 autoreset: bool = False, final_obs: bool = False):
         self.L = _abi.lib()
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
@@ -81,16 +81,42 @@ class TdmWorld:
         for t in range(cfg.n_teams):
             team += [t] * cfg.team_size[t]
         self.team = np.array(team, np.int32)
+        self.final_obs = self.final_mask = self.final_length = self.final_ends = None  # set_final_outputs
         if autoreset:
             self.set_autoreset(True)
+        if final_obs:
+            self.set_final_outputs(True)
 
     def set_autoreset(self, on: bool = True) -> None:
         """Autoreset (macm_tdm_set_autoreset; off at creation): an env that ends (a team wiped out, or
         the time limit) starts its next episode before its next step, as reset_envs(done) would, in
         step() and inside every rollout launch. The outputs of such a step keep the terminal done,
-        winner, health and alive; obs and mask of the reset envs are the new episode's. Needs the
-        device streams of reset(): a placed world raises MacmError from step() and the rollouts."""
+        winner, health and alive; obs and mask of the reset envs are the new episode's
+        (set_final_outputs keeps the ones it overwrites). Needs the device streams of reset(): a placed
+        world raises MacmError from step() and the rollouts."""
         _abi.check(self.L.macm_tdm_set_autoreset(self.h, 1 if on else 0), "macm_tdm_set_autoreset")
+
+    def set_final_outputs(self, on: bool = True) -> None:
+        """Keep each ended episode's last observation (macm_tdm_set_final_outputs), as
+        World.set_final_outputs: with autoreset on, row e of ``final_obs`` [E, N, N-1, 4] and
+        ``final_mask`` [E, N, N-1] holds what the step that ended env e's episode wrote before the reset
+        overwrote it, ``final_length`` [E] that episode's steps and ``final_ends`` [E] counts the ends
+        (int32, zero at first). Per env: the last end of a launch remains. ``on=False`` drops them."""
+        if not on:
+            _abi.check(self.L.macm_tdm_set_final_outputs(self.h, None), "macm_tdm_set_final_outputs")
+            self.final_obs = self.final_mask = self.final_length = self.final_ends = None
+            return
+        kw = dict(pin_memory=True) if self.host_outputs else dict(device=self.device)
+        obs = torch.zeros_like(self.obs, **kw)
+        mask = torch.zeros_like(self.mask, **kw)
+        length = torch.zeros((self.E,), dtype=torch.int32, **kw)
+        ends = torch.zeros((self.E,), dtype=torch.int32, **kw)
+        self._register_final(_abi.MacmFinalOutputs(_ptr(obs), None, _ptr(mask), _ptr(length), _ptr(ends)))
+        self.final_obs, self.final_mask, self.final_length, self.final_ends = obs, mask, length, ends
+
+    def _register_final(self, fin: "_abi.MacmFinalOutputs") -> None:
+        # the library keeps the pointers: whoever calls this keeps the buffers alive
+        _abi.check(self.L.macm_tdm_set_final_outputs(self.h, ctypes.byref(fin)), "macm_tdm_set_final_outputs")
 
     def __del__(self):
         h = getattr(self, "h", None)

@@ -10,6 +10,10 @@ launch per step, with actions and outputs as device tensors:
 Env e is the reference env constructed after ``random.seed(seed + env_offset + e)``;
 each env keeps that stream on the device, so ``reset_envs(mask)`` / ``autoreset=True``
 start new episodes exactly as the env's own ``reset()`` would draw them.
+With ``autoreset=True, final_obs=True`` the observation each ended episode ended on, which the
+reset overwrites in the step's outputs, is kept per env in ``final_obs`` / ``final_nbr_id``, with
+``final_length`` and ``final_ends`` (a gym VecEnv's ``info["terminal_observation"]`` is
+``final_obs[done]``).
 ``seed`` must be >= 0 and every env's seed ``seed + env_offset + e`` must lie in [0, 2**64): the
 C-ABI cannot honour ``random.seed``'s meaning outside it (a negative seed's absolute value, keys of
 three or more words), so the constructor and ``reset`` raise ValueError there (World.reset).
@@ -28,7 +32,8 @@ from gym_macm.world import World
 
 class FlockVec(object):
     def __init__(self, num_envs, n_agents=(10,), targets=None, seed=0, env_offset=0, device=None,
-                 obs_dtype=torch.float32, max_contacts=0, autoreset=False, validate_actions=False, **kwargs):
+                 obs_dtype=torch.float32, max_contacts=0, autoreset=False, validate_actions=False, final_obs=False,
+                 **kwargs):
         self.settings = flockSettings(**kwargs)
         self.num_envs = int(num_envs)
         self.n_agents = list(n_agents) if not isinstance(n_agents, int) else [n_agents]
@@ -45,11 +50,33 @@ class FlockVec(object):
         self.autoreset = bool(autoreset)
         if self.autoreset:
             self.world.set_autoreset(True)
+        if final_obs:  # the ended episodes' last observations (World.set_final_outputs)
+            self.world.set_final_outputs(True)
         self.obs, self.nbr_id = self.world.reset(self.seed, self.env_offset)
 
     @property
     def obs_dim(self):
         return self.world.OD
+
+    # final_obs=True: what the autoreset overwrote, per env (World.set_final_outputs); None otherwise
+    @property
+    def final_obs(self):
+        """[E, N, OD]: row e is the observation env e's last ended episode ended on."""
+        return self.world.final_obs
+
+    @property
+    def final_nbr_id(self):
+        return self.world.final_nbr_id
+
+    @property
+    def final_length(self):
+        """[E] int32: the steps of env e's last ended episode."""
+        return self.world.final_length
+
+    @property
+    def final_ends(self):
+        """[E] int32: env e's episode ends since the tensor was last zeroed."""
+        return self.world.final_ends
 
     def reset(self, seed=None):
         if seed is not None:
@@ -61,7 +88,8 @@ class FlockVec(object):
         """One step of every env. With ``autoreset``, envs whose episode ended in this
         step start their next episode right away (reset_envs on the done flags, on
         the device): the returned done marks them and obs already holds the new
-        episode's initial observation for those envs.
+        episode's initial observation for those envs (with ``final_obs=True`` the observation the
+        episode ended on is ``final_obs[done]``).
 
         Raises MacmOverflowError (a MacmLibraryError) once an earlier step has overflowed a
         capacity (the contact list's max_contacts; dense touching contacts never overflow: the

@@ -110,6 +110,7 @@ class World:
         self._out = _abi.MacmOutputs(_ptr(self.obs), _ptr(self.nbr_id), _ptr(self.reward), _ptr(self.collided),
                                      _ptr(self.done))
         self._out_obs = _abi.MacmOutputs(_ptr(self.obs), _ptr(self.nbr_id), None, None, None)
+        self.final_obs = self.final_nbr_id = self.final_length = self.final_ends = None  # set_final_outputs
 
     def __del__(self):
         h = getattr(self, "h", None)
@@ -163,9 +164,36 @@ class World:
         """Autoreset (macm_world_set_autoreset; off at creation): an env whose step sets done starts
         its next episode before its next step, as reset_envs(done) would, in step() and inside every
         rollout launch. The outputs of such a step keep the terminal done / reward / collided; obs and
-        nbr_id of the reset envs are the new episode's initial observation. Needs the device streams
-        of reset(): a placed world raises MacmError from step() and the rollouts."""
+        nbr_id of the reset envs are the new episode's initial observation (set_final_outputs keeps the
+        ones it overwrites). Needs the device streams of reset(): a placed world raises MacmError from
+        step() and the rollouts."""
         _abi.check(self.L.macm_world_set_autoreset(self.h, 1 if on else 0), "macm_world_set_autoreset")
+
+    def set_final_outputs(self, on: bool = True) -> None:
+        """Keep each ended episode's last observation (macm_world_set_final_outputs). With autoreset on,
+        the reset overwrites obs / nbr_id of the step that set done with the new episode's initial
+        observation; with this on, row e of ``final_obs`` [E, N, OD] and ``final_nbr_id`` [E, N] holds
+        what that step of env e wrote (what it returns with autoreset off: the observation a time-limit
+        truncation bootstraps from), ``final_length`` [E] the ended episode's steps, and ``final_ends``
+        [E] counts env e's episode ends (both int32, zero at first; zero ``final_ends`` again to count
+        afresh). Rows are per env: after a launch in which an env ended twice, the last end's remain.
+        The tensors are owned by this object, on its device (pinned with host_outputs), and stay
+        registered until ``on=False``, which drops them. Nothing is written with autoreset off."""
+        if not on:
+            _abi.check(self.L.macm_world_set_final_outputs(self.h, None), "macm_world_set_final_outputs")
+            self.final_obs = self.final_nbr_id = self.final_length = self.final_ends = None
+            return
+        kw = dict(pin_memory=True) if self.host_outputs else dict(device=self.device)
+        obs = torch.zeros_like(self.obs, **kw)
+        nbr = torch.zeros_like(self.nbr_id, **kw)
+        length = torch.zeros((self.E,), dtype=torch.int32, **kw)
+        ends = torch.zeros((self.E,), dtype=torch.int32, **kw)
+        self._register_final(_abi.MacmFinalOutputs(_ptr(obs), _ptr(nbr), None, _ptr(length), _ptr(ends)))
+        self.final_obs, self.final_nbr_id, self.final_length, self.final_ends = obs, nbr, length, ends
+
+    def _register_final(self, fin: "_abi.MacmFinalOutputs") -> None:
+        # the library keeps the pointers: whoever calls this keeps the buffers alive
+        _abi.check(self.L.macm_world_set_final_outputs(self.h, ctypes.byref(fin)), "macm_world_set_final_outputs")
 
     # -- hot path ------------------------------------------------------------
     def step(self, actions: torch.Tensor):

@@ -22,7 +22,8 @@
  *     Nothing aborts or throws across the ABI.
  *   - "device pointer" = memory the HIP runtime can dereference in a kernel
  *     (hipMalloc / torch CUDA tensor data_ptr()). Output buffers are borrowed for
- *     the duration of the call only; the world owns its state.
+ *     the duration of the call only; the world owns its state. (The one exception:
+ *     macm_final_outputs, which a world keeps until they are replaced or cleared.)
  *   - stream = hipStream_t passed as void* (NULL = default stream). Calls are
  *     asynchronous on that stream; completion is the caller's synchronisation.
  *   - A world is bound to one device. Calls on one world are not thread-safe.
@@ -377,8 +378,45 @@ int macm_world_reset_envs(macm_world* w, const uint8_t* env_mask, const macm_out
  * resync it. With autoreset on and no device streams (the world was placed, not reset) step and
  * every rollout return MACM_E_INVALID with reset_envs' message and launch nothing. A NULL world gives
  * MACM_E_INVALID. Additive: no struct changed, MACM_ABI_VERSION stays 9.
+ * The obs and nbr_id that the reset overwrites are kept where macm_world_set_final_outputs says.
  */
 int macm_world_set_autoreset(macm_world* w, int32_t on);
+
+/*
+ * Where an autoreset world keeps what the reset would otherwise overwrite (device pointers,
+ * NULL = not wanted): the observation an episode ended on, which value bootstrapping at a time-limit
+ * truncation needs (gym's info["terminal_observation"] / final_observation).
+ *
+ * Lifetime: the world keeps a copy of this struct, not of the buffers, until
+ * macm_*_set_final_outputs replaces or clears it (fin NULL, or every field NULL) or the world is
+ * destroyed; the caller keeps the buffers alive that long. This is the one exception to "outputs are
+ * borrowed for the call".
+ *
+ * With autoreset on, whenever the step of env e sets done, row e of every set field is written before
+ * the reset touches the step's output row, in macm_*_step and in every rollout form, on every path:
+ *   obs, nbr_id (TDM: obs, mask)  what that step wrote to its output row (row k of a trajectory), bit
+ *                                 for bit what the same step returns with autoreset off;
+ *   length[e]                     the ended episode's env steps;
+ *   ends[e]                       incremented by 1.
+ * Rows of envs that did not end are not touched; with autoreset off nothing is ever written; reset,
+ * reset_envs and place never write. The slots are per env, not per trajectory row: if an env ends more
+ * than once inside one launch, the last end's values remain and ends counts all of them (a caller that
+ * needs every end keeps n_steps at or below the shortest possible episode, or reads ends).
+ * The rows are copied from the call's output row, so a call on an autoreset world with fin.obs set
+ * needs its own out / traj obs set, and likewise nbr_id and mask: otherwise it returns MACM_E_INVALID
+ * and steps no env.
+ */
+typedef struct macm_final_outputs {
+  void*    obs;     /* Flock [E, N, OD], TDM [E, N, N-1, 4]; float32/float64 as config.obs_f64; 16-byte aligned */
+  int32_t* nbr_id;  /* Flock [E, N]; ignored by TDM   */
+  uint8_t* mask;    /* TDM [E, N, N-1]; ignored by Flock */
+  int32_t* length;  /* [E] env steps of the episode that ended (step_count after its last step) */
+  int32_t* ends;    /* [E] += 1 at every episode end of env e (the caller zeroes it) */
+} macm_final_outputs;
+
+/* NULL or all-NULL: none. MACM_E_INVALID for a NULL world or an obs that is not 16-byte aligned
+ * (nothing changes then). Additive: MACM_ABI_VERSION stays 9. */
+int macm_world_set_final_outputs(macm_world* w, const macm_final_outputs* fin);
 
 /*
  * One env.step for all E envs.
@@ -518,8 +556,12 @@ int macm_tdm_reset_envs(macm_tdm* w, const uint8_t* env_mask, const macm_tdm_out
  * Rollouts of such a world observe inside the step: macm_tdm_launch_flags reports 0 and
  * macm_tdm_reserve is a no-op. Status, placed worlds and NULL as for macm_world_set_autoreset.
  * Additive: no struct changed, MACM_ABI_VERSION stays 9.
+ * The obs and mask that the reset overwrites are kept where macm_tdm_set_final_outputs says.
  */
 int macm_tdm_set_autoreset(macm_tdm* w, int32_t on);
+
+/* As macm_world_set_final_outputs (macm_final_outputs: obs, mask, length, ends; nbr_id ignored). */
+int macm_tdm_set_final_outputs(macm_tdm* w, const macm_final_outputs* fin);
 
 /*
  * One TDM.step for all E envs (combat.py:104-184). actions: device uint8
