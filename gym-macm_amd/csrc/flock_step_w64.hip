@@ -1029,14 +1029,19 @@ struct __align__(16) EnvCarry {
 // to read).
 // NEARL (Flock rollouts, NCAP = 64): the nearest neighbour from the candidate lists kept in LDS between
 // the steps of a launch (above near_build); near_ctl: kNearCtl* bits.
-template <int MODE, int NCAP, typename OT, bool SCAL = false, bool CARRY = false, bool NEARL = false>
+// EV (TDM worlds with events registered, macm_tdm_set_events): hit_out[e, i] = the body agent i's attack
+// damaged in this step, or -1, stored where health_out is; the kernels without it are the ones
+// every other world launches, instruction for instruction what they were before events existed.
+template <int MODE, int NCAP, typename OT, bool SCAL = false, bool CARRY = false, bool NEARL = false, bool EV = false>
 __device__ __attribute__((always_inline)) inline void step_w64_body(
     const StepParams& P, const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur,
     const void* __restrict__ actions, OT* __restrict__ obs, int32_t* __restrict__ nbr_out,
     float* __restrict__ rew_out, uint8_t* __restrict__ coll_out, uint8_t* __restrict__ done_out,
     const int e = blockIdx.x, const int lane = threadIdx.x, TailObs* tl = nullptr, StepCarry* carry = nullptr,
-    const void* actions_next = nullptr, void** pool_out = nullptr, const int near_ctl = 0) {
+    const void* actions_next = nullptr, void** pool_out = nullptr, const int near_ctl = 0,
+    int32_t* __restrict__ hit_out = nullptr) {
   constexpr bool kT = MODE == kTdm;
+  static_assert(!EV || kT, "combat events are TDM's");
   // Flock in the rollout translation units: the f64 polynomial constants from scalar registers
   constexpr bool kPin = MACM_KS_PIN_FLOCK && !kT;
   static_assert(!CARRY || !kT, "the carried step is Flock's");
@@ -1333,12 +1338,17 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
         // listener.hit / listener.fixture persist across casts and steps (literal), or
         // reset per cast (fresh_raycast); damage in agent order (combat.py:152-153)
         for (unsigned long long m = att_m; m; m &= m - 1ull) {
-          const int h = s_hit[__builtin_ctzll(m)];
+          const int k = __builtin_ctzll(m);
+          const int h = s_hit[k];
           if (TP.fresh_raycast) {
             if (h >= 0) s_hpd[h] -= TP.melee_dmg;
           } else {
             if (h >= 0) lis = make_int2(1, h);
             if (lis.x) s_hpd[lis.y] -= TP.melee_dmg;
+            // the damaged body, the listener's after this cast, back into the attacker's entry (N <= 64:
+            // an int8); fresh_raycast: the entry already is it. Each lane picks its entry up where it
+            // stores health_out (nothing else writes s_hit within the step: no register held till then)
+            if constexpr (EV) s_hit[k] = (int8_t)(lis.x ? lis.y : -1);
           }
         }
       }
@@ -1490,6 +1500,7 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
         TB.alive[ag] = act ? 1 : 0;
         if (TB.health_out) TB.health_out[ag] = hp;
         if (TB.alive_out) TB.alive_out[ag] = act ? 1 : 0;
+        if constexpr (EV) hit_out[ag] = att_m ? (int)s_hit[lane] : -1;  // no attack in the env: s_hit is stale
       }
       if (lane == 0) {
         TB.listener[e] = lis;
@@ -2397,6 +2408,7 @@ __device__ __attribute__((always_inline)) inline void step_w64_body(
       TB.alive[ag] = act ? 1 : 0;
       if (TB.health_out) TB.health_out[ag] = hp;
       if (TB.alive_out) TB.alive_out[ag] = act ? 1 : 0;
+      if constexpr (EV) hit_out[ag] = att_m ? (int)s_hit[lane] : -1;  // no attack in the env: s_hit is stale
     }
     s_ang[lane] = ang;
     __syncthreads();
@@ -2732,6 +2744,25 @@ struct RolloutArgs {  // the kernel's only argument (kernarg offset 0)
   unsigned int tail_tag;
   int tail_k0;  // the first step observed in the tail (0: all); the steps before observe in the step
 };
+// The rollout kernels of a TDM world with events registered (macm_tdm_set_events) are instantiated
+// with the observation type tagged, ObsEv<float> / ObsEv<double>: the same kernel templates, and their
+// argument grows by the event pointer.
+template <typename OT>
+struct ObsEv {};
+template <typename OTA>
+struct ObsTag {
+  using type = OTA;
+  static constexpr bool ev = false;
+};
+template <typename OT>
+struct ObsTag<ObsEv<OT>> {
+  using type = OT;
+  static constexpr bool ev = true;
+};
+template <typename OT>
+struct RolloutArgs<ObsEv<OT>> : RolloutArgs<OT> {
+  int32_t* hit_out;  // [E, N], or [K, E, N] with traj (last: the fields before it keep their offsets)
+};
 // Carried Flock rollouts (CARRY) only: this bit of RolloutArgs::cur is MACM_DEBUG_ROLLOUT_RELOAD, every
 // step loads its state and waits for the stores of the step before, as a rollout without the carry.
 // (Not a field of its own: the argument layout of the other rollout kernels stays the measured one.)
@@ -2796,8 +2827,15 @@ __global__ __launch_bounds__(1024) void rollout_sched(const uint32_t* __restrict
 // and the next step's actions in registers between steps (StepCarry) and takes the fence only before a
 // step that has to load. The closed loop (the bot reads the obs the step just stored) and TDM run
 // the instantiations without it.
-template <int MODE, int NCAP, typename OT, bool SCAL = false, bool CARRY = false>
-__global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env_rollout_w64(RolloutArgs<OT> A0) {
+// OTA is the observation type OT, or ObsEv<OT> (TDM worlds with events registered: RolloutArgs then
+// carries hit_out, which advances a row per step of a trajectory as health_out does; the observe-only
+// blocks of the tail write no events). The tag rides on the existing parameter so that the kernels
+// without events keep their names and their code, instruction for instruction.
+template <int MODE, int NCAP, typename OTA, bool SCAL = false, bool CARRY = false>
+__global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env_rollout_w64(RolloutArgs<OTA> A0) {
+  using OT = typename ObsTag<OTA>::type;
+  constexpr bool EV = ObsTag<OTA>::ev;
+  static_assert(!EV || MODE == kTdm, "combat events are TDM's");
   const int nsteps = A0.nsteps;
   const bool bal = A0.B.sched && nsteps >= kRollBalanceMinSteps;  // as in launch_roll
   // TDM tail observation: blocks beyond the envs only observe (TailObs)
@@ -2822,10 +2860,10 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
   for (int k = 0; k < ksteps; ++k) {
     // each step reads its parameters from the kernel arguments afresh, through a pointer the
     // compiler cannot see through, so nothing derived from them stays live across the loop
-    const __attribute__((address_space(4))) RolloutArgs<OT>* ka =
-        (const __attribute__((address_space(4))) RolloutArgs<OT>*)__builtin_amdgcn_kernarg_segment_ptr();
+    const __attribute__((address_space(4))) RolloutArgs<OTA>* ka =
+        (const __attribute__((address_space(4))) RolloutArgs<OTA>*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(ka));
-    const RolloutArgs<OT>& A = *(const RolloutArgs<OT>*)ka;
+    const RolloutArgs<OTA>& A = *(const RolloutArgs<OTA>*)ka;
     const int N = A.P.n_agents, lane = threadIdx.x;
     const size_t EN = (size_t)A.P.n_envs * N;
     const size_t kr = A.traj ? (size_t)k : 0;  // output row of this step
@@ -2842,6 +2880,8 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
       TB.snap_out = A.tail_tag ? (k >= A.tail_k0 ? traj_row(TB.snap_out, (size_t)(k - A.tail_k0), EN) : nullptr)
                                : traj_row(TB.snap_out, kr, EN);
     }
+    int32_t* hit_out = nullptr;
+    if constexpr (EV) hit_out = A.hit_out + kr * EN;
     const size_t abytes = MODE == kTdm ? 4 : 3;  // closed loop: uint8 actions per agent
     uint8_t* const pol_in = A.policy_act ? A.policy_act + kr * EN * abytes : nullptr;
     __builtin_amdgcn_s_setprio(0);  // as at a launch: the chain raises it again
@@ -2867,12 +2907,12 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
       if (!cy.valid) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __syncthreads();
     } else {
-      step_w64_body<MODE, NCAP, OT, SCAL, false, kNearL>(
+      step_w64_body<MODE, NCAP, OT, SCAL, false, kNearL, EV>(
           A.P, A.B, A.TP, TB, kNearL ? (A.cur ^ k) & 1 : A.cur ^ (k & 1),
           pol_in ? pol_in : static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride, obs,
           traj_row(A.nbr_out, kr, EN), traj_row(A.rew_out, kr, EN), traj_row(A.coll_out, kr, EN),
           traj_row(A.done_out, kr, (size_t)A.P.n_envs), env, sl, MODE == kTdm ? &tl : nullptr, nullptr, nullptr, nullptr,
-          near_ctl);
+          near_ctl, hit_out);
       // the next step reads only what this wave wrote: workgroup scope (this CU's L1 and its XCD's L2)
       // suffices; agent scope would write back and invalidate the L2 every step (5x slower, measured)
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -2907,8 +2947,9 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
       int sl = (int)threadIdx.x;
       asm volatile("" : "+v"(sl));
       while (tl.more)
-        step_w64_body<MODE, NCAP, OT, SCAL>(A0.P, A0.B, A0.TP, A0.TB, A0.cur, nullptr, A0.obs, nullptr, nullptr, nullptr,
-                                            nullptr, env, sl, &tl);
+        // (the instantiation of the loop above, EV included: its LDS arrays are this call's too)
+        step_w64_body<MODE, NCAP, OT, SCAL, false, false, EV>(A0.P, A0.B, A0.TP, A0.TB, A0.cur, nullptr, A0.obs, nullptr,
+                                                              nullptr, nullptr, nullptr, env, sl, &tl);
     }
   }
 }
@@ -2920,13 +2961,19 @@ int tdm_rollout_resident_blocks(int n_agents, bool obs_f64) {
                                             : (const void*)env_rollout_w64<kTdm, 32, float>)
                                  : (obs_f64 ? (const void*)env_rollout_w64<kTdm, 64, double>
                                             : (const void*)env_rollout_w64<kTdm, 64, float>);
-  int per = 0, dev = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, W, 0) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
+  // the kernel of worlds with events registered: the same LDS and register budget, asked all the same
+  const void* kev = n_agents <= 32 ? (obs_f64 ? (const void*)env_rollout_w64<kTdm, 32, ObsEv<double>>
+                                              : (const void*)env_rollout_w64<kTdm, 32, ObsEv<float>>)
+                                   : (obs_f64 ? (const void*)env_rollout_w64<kTdm, 64, ObsEv<double>>
+                                              : (const void*)env_rollout_w64<kTdm, 64, ObsEv<float>>);
+  int per = 0, per_ev = 0, dev = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, W, 0) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_ev, kev, W, 0) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
     (void)hipGetLastError();
     return 0;
   }
-  return per * cus;
+  return (per < per_ev ? per : per_ev) * cus;
 }
 
 template <int MODE, int NCAP, typename OT, bool SCAL = false>
@@ -2934,7 +2981,8 @@ static void launch_roll(int nsteps, unsigned long long astride, int traj, hipStr
                         const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur, const void* actions,
                         void* obs, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done,
                         unsigned long long* tail_ctl = nullptr, unsigned tail_tag = 0u, int tail_workers = 0,
-                        int tail_k0 = 0, int reload = 0) {  // reload: bit 0 MACM_DEBUG_ROLLOUT_RELOAD, bit 1 _NEAR_PLAIN
+                        int tail_k0 = 0, int reload = 0,  // reload: bit 0 MACM_DEBUG_ROLLOUT_RELOAD, bit 1 _NEAR_PLAIN
+                        int32_t* hit_out = nullptr) {     // TDM: non-NULL, the kernel that records the events
   // astride == 0: closed loop, `actions` is the bots' action buffer (macm_world_rollout_bots)
   uint8_t* pol = astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(actions)) : nullptr;
   const bool bal = B.sched && nsteps >= kRollBalanceMinSteps;
@@ -2957,6 +3005,12 @@ static void launch_roll(int nsteps, unsigned long long astride, int traj, hipStr
       return;
     }
     if (NCAP == 64 && (reload & 2)) A.cur |= kRollNearPlainBit;
+  } else if (hit_out) {
+    RolloutArgs<ObsEv<OT>> R;
+    static_cast<RolloutArgs<OT>&>(R) = A;
+    R.hit_out = hit_out;
+    hipLaunchKernelGGL((env_rollout_w64<kTdm, NCAP, ObsEv<OT>>), dim3(blocks), dim3(W), 0, s, R);
+    return;
   }
   hipLaunchKernelGGL((env_rollout_w64<MODE, NCAP, OT, SCAL>), dim3(blocks), dim3(W), 0, s, A);
 }
@@ -3000,22 +3054,22 @@ hipError_t launch_tdm_rollout_w64(const StepParams& P, const WorldBuffers& B, co
                                   const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
                                   uint8_t* done, hipStream_t s, int nsteps, unsigned long long astride, int traj,
                                   unsigned long long* tail_ctl, unsigned tail_tag, int tail_workers,
-                                  int tail_k0) {
+                                  int tail_k0, int32_t* hit_out) {
   const bool small = P.n_agents <= 32;
   if (obs_f64) {
     if (small)
       launch_roll<kTdm, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                    nullptr, done, tail_ctl, tail_tag, tail_workers, tail_k0);
+                                    nullptr, done, tail_ctl, tail_tag, tail_workers, tail_k0, 0, hit_out);
     else
       launch_roll<kTdm, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                    nullptr, done, tail_ctl, tail_tag, tail_workers, tail_k0);
+                                    nullptr, done, tail_ctl, tail_tag, tail_workers, tail_k0, 0, hit_out);
   } else {
     if (small)
       launch_roll<kTdm, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                   nullptr, done, tail_ctl, tail_tag, tail_workers, tail_k0);
+                                   nullptr, done, tail_ctl, tail_tag, tail_workers, tail_k0, 0, hit_out);
     else
       launch_roll<kTdm, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                   nullptr, done, tail_ctl, tail_tag, tail_workers, tail_k0);
+                                   nullptr, done, tail_ctl, tail_tag, tail_workers, tail_k0, 0, hit_out);
   }
   return hipGetLastError();
 }
@@ -3028,6 +3082,16 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
     OT* __restrict__ obs, int32_t* __restrict__ nbr_out, float* __restrict__ rew_out,
     uint8_t* __restrict__ coll_out, uint8_t* __restrict__ done_out) {
   step_w64_body<MODE, NCAP, OT, SCAL>(P, B, TP, TB, cur, actions, obs, nbr_out, rew_out, coll_out, done_out);
+}
+
+// the TDM step of a world with events registered (step_w64_body EV)
+template <int NCAP, typename OT>
+__global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env_step_ev_w64(
+    StepParams P, WorldBuffers B, TdmParams TP, TdmBuffers TB, int cur, const void* __restrict__ actions,
+    OT* __restrict__ obs, uint8_t* __restrict__ done_out, int32_t* __restrict__ hit_out) {
+  step_w64_body<kTdm, NCAP, OT, false, false, false, true>(P, B, TP, TB, cur, actions, obs, nullptr, nullptr, nullptr,
+                                                          done_out, blockIdx.x, threadIdx.x, nullptr, nullptr, nullptr,
+                                                          nullptr, 0, hit_out);
 }
 
 template <typename OT>
@@ -3194,8 +3258,27 @@ hipError_t launch_step_w64(const StepParams& P, const WorldBuffers& B, int cur, 
 
 hipError_t launch_tdm_step_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
-                               uint8_t* done, hipStream_t s) {
+                               uint8_t* done, hipStream_t s, int32_t* hit_out) {
   const bool small = P.n_agents <= 32;
+  if (hit_out) {  // events registered: the kernel that records them
+    const dim3 grid(P.n_envs), block(W);
+    if (obs_f64) {
+      if (small)
+        hipLaunchKernelGGL((env_step_ev_w64<32, double>), grid, block, 0, s, P, B, TP, TB, cur, actions, (double*)obs, done,
+                           hit_out);
+      else
+        hipLaunchKernelGGL((env_step_ev_w64<64, double>), grid, block, 0, s, P, B, TP, TB, cur, actions, (double*)obs, done,
+                           hit_out);
+    } else {
+      if (small)
+        hipLaunchKernelGGL((env_step_ev_w64<32, float>), grid, block, 0, s, P, B, TP, TB, cur, actions, (float*)obs, done,
+                           hit_out);
+      else
+        hipLaunchKernelGGL((env_step_ev_w64<64, float>), grid, block, 0, s, P, B, TP, TB, cur, actions, (float*)obs, done,
+                           hit_out);
+    }
+    return hipGetLastError();
+  }
   if (obs_f64) {
     if (small)
       launch_w64<kTdm, 32, double>(s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr, nullptr, done);

@@ -35,12 +35,12 @@ hipError_t launch_observe_wg(const StepParams& P, const WorldBuffers& B, void* o
                              hipStream_t s);
 hipError_t launch_tdm_step_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
-                               uint8_t* done, hipStream_t s);
+                               uint8_t* done, hipStream_t s, int32_t* hit_out = nullptr);
 hipError_t launch_tdm_rollout_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                   const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
                                   uint8_t* done, hipStream_t s, int nsteps, unsigned long long astride, int traj,
                                   unsigned long long* tail_ctl = nullptr, unsigned tail_tag = 0u, int tail_workers = 0,
-                                  int tail_k0 = 0);
+                                  int tail_k0 = 0, int32_t* hit_out = nullptr);
 int tdm_rollout_resident_blocks(int n_agents, bool obs_f64);
 // worlds with autoreset on (flock_rollout_ar_w64.hip): the rollout with the in-launch episode reset
 hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
@@ -50,7 +50,7 @@ hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int
 hipError_t launch_tdm_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                      const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
                                      uint8_t* done, hipStream_t s, int nsteps, unsigned long long astride, int traj,
-                                     uint32_t* mt, const PoseDraw& D, const FinalOut& F);
+                                     uint32_t* mt, const PoseDraw& D, const FinalOut& F, int32_t* hit_out = nullptr);
 hipError_t launch_tdm_init_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                const TdmBuffers& TB, int cur, void* obs, bool obs_f64, const uint8_t* mask,
                                hipStream_t s);
@@ -60,7 +60,8 @@ hipError_t launch_final_copy(const uint8_t* mask, const FinalOut& F, const void*
                              const uint8_t* msk, const int32_t* step_count, unsigned long long obs_bytes, int n_nbr,
                              int n_msk, int n_envs, hipStream_t s);
 hipError_t launch_tdm_step_wg(const StepParams& P, const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB,
-                              int cur, const void* actions, void* obs, bool obs_f64, uint8_t* done, hipStream_t s);
+                              int cur, const void* actions, void* obs, bool obs_f64, uint8_t* done, hipStream_t s,
+                              int32_t* hit_out = nullptr);
 hipError_t launch_tdm_init_wg(const StepParams& P, const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB,
                               int cur, void* obs, bool obs_f64, const uint8_t* mask, hipStream_t s);
 hipError_t launch_tdm_observe_wg(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
@@ -142,6 +143,9 @@ struct macm_tdm {
   bool mt_valid = false;
   bool autoreset = false;  // macm_tdm_set_autoreset
   FinalOut fin{};          // macm_tdm_set_final_outputs
+  // macm_tdm_set_events: the caller's buffer, kept until replaced or cleared (hit_id NULL: none; the
+  // steps then launch the kernels without events, the ones they have always launched)
+  macm_tdm_events events{nullptr, 0};
   uint32_t* hstat = nullptr;
   unsigned long long* bad = nullptr;
   int slots_alloc = 0;  // as macm_world
@@ -1467,10 +1471,11 @@ static hipError_t tdm_launch_init(const macm_tdm* w, const TdmBuffers& TB, void*
   return launch_tdm_init_wg(w->P, w->B, w->TP, TB, w->cur, obs, w->cfg.obs_f64 != 0, mask, s);
 }
 
+// hit: the row of the registered events this step writes (macm_tdm_set_events), or NULL
 static hipError_t tdm_launch_step(const macm_tdm* w, const TdmBuffers& TB, int cur, const void* actions, void* obs,
-                                  uint8_t* done, hipStream_t s) {
-  if (w->wave) return launch_tdm_step_w64(w->P, w->B, w->TP, TB, cur, actions, obs, w->cfg.obs_f64 != 0, done, s);
-  return launch_tdm_step_wg(w->P, w->B, w->TP, TB, cur, actions, obs, w->cfg.obs_f64 != 0, done, s);
+                                  uint8_t* done, hipStream_t s, int32_t* hit) {
+  if (w->wave) return launch_tdm_step_w64(w->P, w->B, w->TP, TB, cur, actions, obs, w->cfg.obs_f64 != 0, done, s, hit);
+  return launch_tdm_step_wg(w->P, w->B, w->TP, TB, cur, actions, obs, w->cfg.obs_f64 != 0, done, s, hit);
 }
 
 static int tdm_init(macm_tdm* w, const macm_tdm_outputs* out, hipStream_t s) {
@@ -1568,6 +1573,17 @@ int macm_tdm_set_final_outputs(macm_tdm* w, const macm_final_outputs* fin) {
   return MACM_OK;
 }
 
+int macm_tdm_set_events(macm_tdm* w, const macm_tdm_events* ev) {
+  const bool clear = !ev || !ev->hit_id;
+  // the registration itself first: what it says is wrong whatever world it is for
+  if (!clear && reinterpret_cast<uintptr_t>(ev->hit_id) % alignof(int32_t))
+    return fail(MACM_E_INVALID, "events: hit_id must be 4-byte aligned");
+  if (!clear && ev->rows < 1) return fail(MACM_E_INVALID, "events: rows must be >= 1");
+  if (!w) return fail(MACM_E_INVALID, "tdm is NULL");
+  w->events = clear ? macm_tdm_events{nullptr, 0} : *ev;
+  return MACM_OK;
+}
+
 // As world_autoreset_step: the step's done flags (a private copy) mask the draw and init launches.
 // TB / obs: the step's outputs; the init writes the new initial obs and mask there and leaves the
 // terminal health, alive and winner outputs as the step wrote them.
@@ -1659,13 +1675,13 @@ int macm_tdm_step(macm_tdm* w, const void* actions, const macm_tdm_outputs* out,
     const int rc = tdm_split_buffers(w, (size_t)w->P.n_envs, s);
     if (rc) return rc;
     TB.snap_out = w->snap;
-    HIP_TRY(tdm_launch_step(w, TB, w->cur, actions, nullptr, out->done, s));
+    HIP_TRY(tdm_launch_step(w, TB, w->cur, actions, nullptr, out->done, s, w->events.hit_id));
     w->cur ^= 1;
     HIP_TRY(launch_tdm_observe_snap(w->TP, w->P.n_agents, (size_t)w->P.n_envs, w->snap, obs, w->cfg.obs_f64 != 0,
                                     TB.mask_out, s));
     return MACM_OK;
   }
-  HIP_TRY(tdm_launch_step(w, TB, w->cur, actions, obs, out ? out->done : nullptr, s));
+  HIP_TRY(tdm_launch_step(w, TB, w->cur, actions, obs, out ? out->done : nullptr, s, w->events.hit_id));
   w->cur ^= 1;
   if (w->autoreset) return tdm_autoreset_step(w, TB, obs, s);
   return MACM_OK;
@@ -1747,7 +1763,7 @@ static int tdm_rollout_tail(macm_tdm* w, const TdmBuffers& TB, const void* actio
   TdmBuffers TBt = TB;
   TBt.snap_out = w->tail_snap;
   HIP_TRY(launch_tdm_rollout_w64(w->P, w->B, w->TP, TBt, w->cur, actions, out->obs, w->cfg.obs_f64 != 0, out->done, s,
-                                 n_steps, astride, 1, w->tail_ctl, w->tail_tag, tdm_tail_workers(w), k0));
+                                 n_steps, astride, 1, w->tail_ctl, w->tail_tag, tdm_tail_workers(w), k0, w->events.hit_id));
   if (n_steps & 1) w->cur ^= 1;
   return MACM_OK;
 }
@@ -1767,7 +1783,7 @@ static int tdm_rollout_split(macm_tdm* w, const TdmBuffers& TB, const void* acti
     TdmBuffers TBs = TB;
     TBs.snap_out = w->snap;
     HIP_TRY(launch_tdm_rollout_w64(w->P, w->B, w->TP, TBs, w->cur, actions, nullptr, f64, out ? out->done : nullptr, s,
-                                   n_steps, astride, 0));
+                                   n_steps, astride, 0, nullptr, 0u, 0, 0, w->events.hit_id));
     if (n_steps & 1) w->cur ^= 1;
     HIP_TRY(launch_tdm_observe_snap(w->TP, (int)N, E, w->snap, out->obs, f64, TB.mask_out, s));
     return MACM_OK;
@@ -1790,7 +1806,7 @@ static int tdm_rollout_split(macm_tdm* w, const TdmBuffers& TB, const void* acti
     TBc.winner_out = row(TB.winner_out, E);
     TBc.snap_out = snap;
     HIP_TRY(launch_tdm_rollout_w64(w->P, w->B, w->TP, TBc, w->cur, act + (size_t)k0 * astride, nullptr, f64,
-                                   row(out->done, E), s, kc, astride, 1));
+                                   row(out->done, E), s, kc, astride, 1, nullptr, 0u, 0, 0, row(w->events.hit_id, EN)));
     if (kc & 1) w->cur ^= 1;
     HIP_TRY(hipEventRecord(w->ev_phys[b], s));
     HIP_TRY(hipStreamWaitEvent(w->obs_stream, w->ev_phys[b], 0));
@@ -1815,6 +1831,9 @@ static int tdm_rollout(macm_tdm* w, const void* actions, int n_steps, const macm
   if (const int rc = final_outputs_need(w->autoreset, w->fin, out ? out->obs : nullptr, nullptr,
                                         out ? out->mask : nullptr))
     return rc;
+  if (traj && w->events.hit_id && n_steps > w->events.rows)
+    return fail(MACM_E_INVALID, "events: n_steps " + std::to_string(n_steps) + " exceeds the " +
+                                    std::to_string(w->events.rows) + " rows registered (macm_tdm_set_events)");
   if (const uint32_t st = read_host_status(w->hstat)) return overflow_error(st);
   DeviceGuard g(w->device);
   hipStream_t s = (hipStream_t)stream;
@@ -1847,7 +1866,8 @@ static int tdm_rollout(macm_tdm* w, const void* actions, int n_steps, const macm
       TBk.winner_out = row(TB.winner_out, E);
       void* obs_k = out && out->obs ? static_cast<unsigned char*>(out->obs) + kr * obytes : nullptr;
       const unsigned char* act_k = act + k * kstride;
-      HIP_TRY(tdm_launch_step(w, TBk, w->cur, act_k, obs_k, out ? row(out->done, E) : nullptr, s));
+      HIP_TRY(tdm_launch_step(w, TBk, w->cur, act_k, obs_k, out ? row(out->done, E) : nullptr, s,
+                              row(w->events.hit_id, EN)));
       w->cur ^= 1;
       if (w->autoreset) {  // before the bots: a reset env's next actions come from its new initial obs
         const int rc = tdm_autoreset_step(w, TBk, obs_k, s);
@@ -1866,10 +1886,11 @@ static int tdm_rollout(macm_tdm* w, const void* actions, int n_steps, const macm
   if (w->autoreset)  // the kernels with the in-launch reset (the observation inside the step)
     HIP_TRY(launch_tdm_rollout_ar_w64(w->P, w->B, w->TP, TB, w->cur, actions, out ? out->obs : nullptr,
                                       w->cfg.obs_f64 != 0, out ? out->done : nullptr, s, n_steps, astride, traj ? 1 : 0,
-                                      w->mt, tdm_pose_draw(w), w->fin));
+                                      w->mt, tdm_pose_draw(w), w->fin, w->events.hit_id));
   else
     HIP_TRY(launch_tdm_rollout_w64(w->P, w->B, w->TP, TB, w->cur, actions, out ? out->obs : nullptr,
-                                   w->cfg.obs_f64 != 0, out ? out->done : nullptr, s, n_steps, astride, traj ? 1 : 0));
+                                   w->cfg.obs_f64 != 0, out ? out->done : nullptr, s, n_steps, astride, traj ? 1 : 0,
+                                   nullptr, 0u, 0, 0, w->events.hit_id));
   if (n_steps & 1) w->cur ^= 1;
   return MACM_OK;
 }

@@ -188,11 +188,22 @@ struct RolloutArArgs {  // the kernel's only argument (kernarg offset 0)
   PoseDraw D;
   FinalOut F;  // last: the fields before it keep their offsets
 };
+// worlds with events registered (ObsEv, flock_step_w64.hip): A is the plain RolloutArgs still, so the
+// fields above keep their offsets, and the event pointer follows them
+template <typename OT>
+struct RolloutArArgs<ObsEv<OT>> : RolloutArArgs<OT> {
+  int32_t* hit_out;  // [E, N], or [K, E, N] with A.traj
+};
 
 // env_rollout_w64 with the in-launch reset; no tail or split observation (their pose snapshots know
 // nothing of a mid-launch respawn: TDM observes inside the step).
-template <int MODE, int NCAP, typename OT, bool SCAL = false, bool CARRY = false>
-__global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env_rollout_ar_w64(RolloutArArgs<OT> R0) {
+// OTA: OT or ObsEv<OT>, as env_rollout_w64. The step writes the events, the in-launch reset none: it
+// gets no pointer to them, as it gets no health_out.
+template <int MODE, int NCAP, typename OTA, bool SCAL = false, bool CARRY = false>
+__global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env_rollout_ar_w64(RolloutArArgs<OTA> R0) {
+  using OT = typename ObsTag<OTA>::type;
+  constexpr bool EV = ObsTag<OTA>::ev;
+  static_assert(!EV || MODE == kTdm, "combat events are TDM's");
   const int nsteps = R0.A.nsteps;
   const bool bal = R0.A.B.sched && nsteps >= kRollBalanceMinSteps;  // as in launch_roll_ar
   const int env = bal ? (int)R0.A.B.sched[R0.A.sched_off + blockIdx.x] : (int)blockIdx.x;
@@ -202,10 +213,10 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
   int near_keep = 0;
   for (int k = 0; k < nsteps; ++k) {
     // as env_rollout_w64: the arguments afresh every step, through a pointer the compiler cannot see through
-    const __attribute__((address_space(4))) RolloutArArgs<OT>* ka =
-        (const __attribute__((address_space(4))) RolloutArArgs<OT>*)__builtin_amdgcn_kernarg_segment_ptr();
+    const __attribute__((address_space(4))) RolloutArArgs<OTA>* ka =
+        (const __attribute__((address_space(4))) RolloutArArgs<OTA>*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(ka));
-    const RolloutArArgs<OT>& R = *(const RolloutArArgs<OT>*)ka;
+    const RolloutArArgs<OTA>& R = *(const RolloutArArgs<OTA>*)ka;
     const RolloutArgs<OT>& A = R.A;
     const int N = A.P.n_agents, lane = threadIdx.x;
     const size_t EN = (size_t)A.P.n_envs * N;
@@ -220,6 +231,8 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
       TB.alive_out = traj_row(TB.alive_out, kr, EN);
       TB.winner_out = traj_row(TB.winner_out, kr, (size_t)A.P.n_envs);
     }
+    int32_t* hit_out = nullptr;
+    if constexpr (EV) hit_out = R.hit_out + kr * EN;
     const size_t abytes = MODE == kTdm ? 4 : 3;  // closed loop: uint8 actions per agent
     uint8_t* const pol_in = A.policy_act ? A.policy_act + kr * EN * abytes : nullptr;
     __builtin_amdgcn_s_setprio(0);  // as at a launch: the chain raises it again
@@ -235,11 +248,11 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
           traj_row(A.done_out, kr, (size_t)A.P.n_envs), env, sl, nullptr, &cy,
           k + 1 < nsteps ? act_k + A.astride : nullptr, &lds, near_ctl);
     } else {
-      step_w64_body<MODE, NCAP, OT, SCAL, false, kNearL>(
+      step_w64_body<MODE, NCAP, OT, SCAL, false, kNearL, EV>(
           A.P, A.B, A.TP, TB, kNearL ? (A.cur ^ k) & 1 : A.cur ^ (k & 1),
           pol_in ? pol_in : static_cast<const unsigned char*>(A.actions) + (size_t)k * A.astride, obs, nbr,
           traj_row(A.rew_out, kr, EN), traj_row(A.coll_out, kr, EN), traj_row(A.done_out, kr, (size_t)A.P.n_envs), env, sl,
-          nullptr, nullptr, nullptr, &lds, near_ctl);
+          nullptr, nullptr, nullptr, &lds, near_ctl, hit_out);
     }
     // the step's done flag, wave-uniform once broadcast from lane 0, which stored it (a lane's
     // accesses to one address stay in order)
@@ -289,7 +302,7 @@ template <int MODE, int NCAP, typename OT, bool SCAL = false>
 static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hipStream_t s, const StepParams& P,
                            const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur, const void* actions,
                            void* obs, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, int reload, uint32_t* mt,
-                           const PoseDraw& D, const FinalOut& F) {
+                           const PoseDraw& D, const FinalOut& F, int32_t* hit_out = nullptr) {
   // astride == 0: closed loop, `actions` is the bots' action buffer
   uint8_t* pol = astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(actions)) : nullptr;
   if (B.sched && nsteps >= kRollBalanceMinSteps) {  // the balanced env order, as launch_roll
@@ -310,6 +323,12 @@ static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hip
       return;
     }
     if (NCAP == 64 && (reload & 2)) R.A.cur |= kRollNearPlainBit;
+  } else if (hit_out) {  // events registered: the kernel that records them
+    RolloutArArgs<ObsEv<OT>> V;
+    static_cast<RolloutArArgs<OT>&>(V) = R;
+    V.hit_out = hit_out;
+    hipLaunchKernelGGL((env_rollout_ar_w64<kTdm, NCAP, ObsEv<OT>>), dim3(P.n_envs), dim3(W), 0, s, V);
+    return;
   }
   hipLaunchKernelGGL((env_rollout_ar_w64<MODE, NCAP, OT, SCAL>), dim3(P.n_envs), dim3(W), 0, s, R);
 }
@@ -346,22 +365,22 @@ hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int
 hipError_t launch_tdm_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                      const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
                                      uint8_t* done, hipStream_t s, int nsteps, unsigned long long astride, int traj,
-                                     uint32_t* mt, const PoseDraw& D, const FinalOut& F) {
+                                     uint32_t* mt, const PoseDraw& D, const FinalOut& F, int32_t* hit_out) {
   const bool small = P.n_agents <= 32;
   if (obs_f64) {
     if (small)
       launch_roll_ar<kTdm, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                      nullptr, done, 0, mt, D, F);
+                                      nullptr, done, 0, mt, D, F, hit_out);
     else
       launch_roll_ar<kTdm, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                      nullptr, done, 0, mt, D, F);
+                                      nullptr, done, 0, mt, D, F, hit_out);
   } else {
     if (small)
       launch_roll_ar<kTdm, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                     nullptr, done, 0, mt, D, F);
+                                     nullptr, done, 0, mt, D, F, hit_out);
     else
       launch_roll_ar<kTdm, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                     nullptr, done, 0, mt, D, F);
+                                     nullptr, done, 0, mt, D, F, hit_out);
   }
   return hipGetLastError();
 }

@@ -77,6 +77,11 @@ class MacmFinalOutputs(Structure):
     _fields_ = [(n, c_void_p) for n in ("obs", "nbr_id", "mask", "length", "ends")]
 
 
+class MacmTdmEvents(Structure):
+    """macm_tdm_events: where a TDM world writes who damaged whom (hit_id None = not wanted)."""
+    _fields_ = [("hit_id", c_void_p), ("rows", c_int32)]
+
+
 class MacmState(Structure):
     _fields_ = [(n, c_void_p) for n in (
         "pos", "vel", "angle", "fat", "sleep", "targets", "contact_count", "contact_ab",
@@ -230,6 +235,7 @@ SIGNATURES = {
     "macm_tdm_reset_envs": (c_int, [c_void_p, c_void_p, POINTER(MacmTdmOutputs), c_void_p]),
     "macm_tdm_set_autoreset": (c_int, [c_void_p, c_int32]),
     "macm_tdm_set_final_outputs": (c_int, [c_void_p, POINTER(MacmFinalOutputs)]),
+    "macm_tdm_set_events": (c_int, [c_void_p, POINTER(MacmTdmEvents)]),
     "macm_tdm_step": (c_int, [c_void_p, c_void_p, POINTER(MacmTdmOutputs), c_void_p]),
     "macm_tdm_rollout": (c_int, [c_void_p, c_void_p, c_int, POINTER(MacmTdmOutputs), c_void_p]),
     "macm_tdm_rollout_bots": (c_int, [c_void_p, c_void_p, c_int, POINTER(MacmTdmOutputs), c_void_p]),

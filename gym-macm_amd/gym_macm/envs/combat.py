@@ -132,7 +132,9 @@ class TDM(object):
                             decay_mov_penalty=decay_mov_penalty, world_width=self.world_width,
                             world_height=self.world_height)
         # one env: outputs and actions in pinned host memory (zero-copy views)
-        self.world = TdmWorld(cfg, 1, device=device, host_outputs=True)
+        # (events on: who damaged whom in the last step, self.hits; not in the reference)
+        self.world = TdmWorld(cfg, 1, device=device, host_outputs=True, events=True)
+        self.hits = {}
         self._act = torch.ones((1, N, 4), dtype=torch.uint8, pin_memory=True)
         self._act_np = self._act.numpy()
         self._cache = None
@@ -209,6 +211,10 @@ class TDM(object):
         self._cache = None
         alive_before = [agent.alive for agent in self.agents]
         self.obs = self._obs_dict()
+        # {attacker id: id of the body its attack damaged} in this step (TdmWorld.set_events; with the
+        # literal listener that body may be an ally, the attacker itself or already dead)
+        hit = self.world.hit_id[0].numpy()
+        self.hits = {agent.id: self.agents[int(hit[k])].id for k, agent in enumerate(self.agents) if hit[k] >= 0}
         died = False
         for agent, was in zip(self.agents, alive_before):
             if was and not agent.alive:
@@ -256,6 +262,7 @@ class TDM(object):
         self._cache = None
         self.n_alive = self.n_agents.copy()
         self.obs = self._obs_dict()
+        self.hits = {}
         self.create_space()
         return self.obs
 

@@ -45,7 +45,7 @@ class TdmWorld:
     owned by this object and overwritten by every call."""
 
     def __init__(self, cfg: _abi.MacmTdmConfig, n_envs: int = 1, device=None, host_outputs: bool = False,
-                 autoreset: bool = False, final_obs: bool = False):
+                 autoreset: bool = False, final_obs: bool = False, events: bool = False):
         self.L = _abi.lib()
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
@@ -82,10 +82,13 @@ class TdmWorld:
             team += [t] * cfg.team_size[t]
         self.team = np.array(team, np.int32)
         self.final_obs = self.final_mask = self.final_length = self.final_ends = None  # set_final_outputs
+        self.hit_id = None  # set_events
         if autoreset:
             self.set_autoreset(True)
         if final_obs:
             self.set_final_outputs(True)
+        if events:
+            self.set_events(True)
 
     def set_autoreset(self, on: bool = True) -> None:
         """Autoreset (macm_tdm_set_autoreset; off at creation): an env that ends (a team wiped out, or
@@ -117,6 +120,29 @@ class TdmWorld:
     def _register_final(self, fin: "_abi.MacmFinalOutputs") -> None:
         # the library keeps the pointers: whoever calls this keeps the buffers alive
         _abi.check(self.L.macm_tdm_set_final_outputs(self.h, ctypes.byref(fin)), "macm_tdm_set_final_outputs")
+
+    def set_events(self, on: bool = True) -> None:
+        """Combat events (macm_tdm_set_events; off at creation): ``hit_id`` [E, N] int32, -1 at first.
+        After a step, hit_id[e, i] is the env-local index of the body whose health agent i's attack
+        reduced in that step, or -1 (i dead at the step's start, no attack, on cooldown, or nobody
+        damaged). With the literal listener that body is the listener's after i's cast: it may be an
+        ally, i itself or a body already dead. step() and the rollouts write it where they write
+        ``health`` (a rollout leaves the last step's); reset, place, reset_envs, observe and an
+        autoreset never do. trajectory_buffers() then adds ``hit_id`` [K, E, N]. gym_macm.tdm_rewards
+        composes rewards from it. ``on=False`` drops the registration and the tensor."""
+        if not on:
+            _abi.check(self.L.macm_tdm_set_events(self.h, None), "macm_tdm_set_events")
+            self.hit_id = None
+            return
+        kw = dict(pin_memory=True) if self.host_outputs else dict(device=self.device)
+        hit = torch.full((self.E, self.N), -1, dtype=torch.int32, **kw)
+        self._register_events(hit, 1)
+        self.hit_id = hit
+
+    def _register_events(self, hit_id: torch.Tensor, rows: int) -> None:
+        # the library keeps the pointer: whoever calls this keeps the buffer alive
+        ev = _abi.MacmTdmEvents(_ptr(hit_id), int(rows))
+        _abi.check(self.L.macm_tdm_set_events(self.h, ctypes.byref(ev)), "macm_tdm_set_events")
 
     def __del__(self):
         h = getattr(self, "h", None)
@@ -194,15 +220,17 @@ class TdmWorld:
     _TRAJ_KEYS = ("obs", "mask", "health", "alive", "done", "winner")
 
     def trajectory_buffers(self, n_steps: int) -> dict:
-        """[n_steps, ...] output buffers for rollout_traj / rollout_bots_traj (reusable across calls)."""
+        """[n_steps, ...] output buffers for rollout_traj / rollout_bots_traj (reusable across calls);
+        with events on (set_events) also ``hit_id`` [n_steps, E, N] int32."""
         K, E, N, d = int(n_steps), self.E, self.N, self.device
         odt = torch.float64 if self.cfg.obs_f64 else torch.float32
+        ev = dict(hit_id=torch.full((K, E, N), -1, dtype=torch.int32, device=d)) if self.hit_id is not None else {}
         return dict(obs=torch.empty((K, E, N, N - 1, 4), dtype=odt, device=d),
                     mask=torch.empty((K, E, N, N - 1), dtype=torch.uint8, device=d),
                     health=torch.empty((K, E, N), dtype=torch.float64, device=d),
                     alive=torch.empty((K, E, N), dtype=torch.uint8, device=d),
                     done=torch.empty((K, E), dtype=torch.uint8, device=d),
-                    winner=torch.empty((K, E), dtype=torch.int32, device=d))
+                    winner=torch.empty((K, E), dtype=torch.int32, device=d), **ev)
 
     def _traj_call(self, fn, name, actions, K, traj):
         traj = self.trajectory_buffers(K) if traj is None else traj
@@ -210,12 +238,30 @@ class TdmWorld:
         E, N = self.E, self.N
         spec = dict(obs=(odt, (E, N, N - 1, 4)), mask=(torch.uint8, (E, N, N - 1)), health=(torch.float64, (E, N)),
                     alive=(torch.uint8, (E, N)), done=(torch.uint8, (E,)), winner=(torch.int32, (E,)))
-        out = _abi.MacmTdmOutputs(*[_ptr(t) for t in check_traj(traj, spec, K, self.device, self._TRAJ_KEYS)])
-        _abi.check(fn(self.h, _ptr(actions), K, ctypes.byref(out), self._stream()), name)
+        keys = self._TRAJ_KEYS
+        if self.hit_id is not None:  # events on: the dict carries hit_id too
+            spec["hit_id"] = (torch.int32, (E, N))
+            keys = keys + ("hit_id",)
+        bufs = check_traj(traj, spec, K, self.device, keys)
+        out = _abi.MacmTdmOutputs(*[_ptr(t) for t in bufs[:6]])
+        hit = None
+        if self.hit_id is not None and K > 0:
+            # the trajectory's rows are registered for this call, then the world's own again
+            hit = bufs[6]
+            if hit is None:
+                raise ValueError("events are on: the trajectory buffers need 'hit_id' (trajectory_buffers adds it)")
+            self._register_events(hit, K)
+        try:
+            _abi.check(fn(self.h, _ptr(actions), K, ctypes.byref(out), self._stream()), name)
+        finally:
+            if hit is not None:
+                self._register_events(self.hit_id, 1)
         if K > 0:  # the world's own buffers keep the current step's outputs
             for k in self._TRAJ_KEYS:
                 if traj.get(k) is not None:
                     getattr(self, k).copy_(traj[k][K - 1])
+            if hit is not None:
+                self.hit_id.copy_(hit[K - 1])
         return traj
 
     def rollout_traj(self, actions: torch.Tensor, traj: dict = None) -> dict:

@@ -564,6 +564,38 @@ int macm_tdm_set_autoreset(macm_tdm* w, int32_t on);
 int macm_tdm_set_final_outputs(macm_tdm* w, const macm_final_outputs* fin);
 
 /*
+ * Combat events: who damaged whom, per agent and per step. The reference's TDM has no reward
+ * (get_rewards is `pass`) and a health trajectory does not say whose attack did the damage; the
+ * ordered listener update inside the step is the only place that knows, and this exports it.
+ *
+ * hit_id[e, i] of one step is the env-local index j of the body whose health agent i's attack
+ * reduced in that step, or -1: i was dead at the step's start, its attack bit was 0, its
+ * cooldown_atk was above 0, or its attack damaged nobody (fresh_raycast: the ray hit no one; the
+ * literal listener: nothing has been hit yet in this episode). With the literal listener j is the
+ * listener's body after i's cast: the body i's ray hit, or else the last body any earlier cast of
+ * the episode hit, which may be an ally, i itself or a body that is already dead.
+ *
+ * Every step that writes an env's `health` output also writes all N entries of the env's row; an
+ * env left unstepped (MACM_ST_SPILL_WAIT) keeps its row. macm_tdm_reset, _place, _reset_envs,
+ * _observe and the reset of an autoreset world never write events: a terminal step's row keeps what
+ * the step wrote, as health, alive and winner do.
+ * macm_tdm_step, _rollout and _rollout_bots write row 0 (rollouts: the last step's row remains);
+ * macm_tdm_rollout_traj and _rollout_bots_traj write step k into row k and return MACM_E_INVALID,
+ * stepping nothing, when n_steps > rows.
+ *
+ * A registration, as macm_tdm_set_final_outputs: the world keeps a copy of the struct, not of the
+ * buffer, which must stay valid until the registration is replaced or cleared (ev NULL, or hit_id
+ * NULL) or the world is destroyed. MACM_E_INVALID with a message, nothing changed: a NULL world, a
+ * misaligned hit_id, rows < 1 with a non-NULL hit_id. With nothing registered every call launches
+ * the kernels it launched before events existed. Additive: no struct changed, MACM_ABI_VERSION stays 9.
+ */
+typedef struct macm_tdm_events {
+  int32_t* hit_id; /* [rows, E, N]; device or host-mapped pointer, 4-byte aligned; NULL = none */
+  int32_t rows;    /* rows the caller allocated (>= 1)                                         */
+} macm_tdm_events;
+int macm_tdm_set_events(macm_tdm* w, const macm_tdm_events* ev);
+
+/*
  * One TDM.step for all E envs (combat.py:104-184). actions: device uint8
  * [E, N, 4] (MultiDiscrete([3,3,3,2]): forward, lateral, rotation, attack);
  * rows of dead agents are ignored. An env with more than 256 touching contacts or a body touching
