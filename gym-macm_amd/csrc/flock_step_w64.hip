@@ -50,6 +50,7 @@
 //     velocity/impulse component, never a nonzero value or any position.
 //   * circles sit at the body origin, so b2Mul(xf, m_p) == position exactly.
 #include "bots.hpp"
+#include "policy_mlp.hpp"
 #include "flock_common.hpp"
 #include "flock_spill.hpp"
 #include "tdm_obs.hpp"
@@ -2749,20 +2750,46 @@ struct RolloutArgs {  // the kernel's only argument (kernarg offset 0)
 // argument grows by the event pointer.
 template <typename OT>
 struct ObsEv {};
+// The closed loop of a Flock world under a registered policy (macm_world_rollout_policy) likewise:
+// ObsPol<float> / ObsPol<double>, the same kernel templates with the MLP of policy_mlp.hpp where the
+// bot is, and their argument grows by the policy's fields.
+template <typename OT>
+struct ObsPol {};
 template <typename OTA>
 struct ObsTag {
   using type = OTA;
   static constexpr bool ev = false;
+  static constexpr bool pol = false;
 };
 template <typename OT>
 struct ObsTag<ObsEv<OT>> {
   using type = OT;
   static constexpr bool ev = true;
+  static constexpr bool pol = false;
+};
+template <typename OT>
+struct ObsTag<ObsPol<OT>> {
+  using type = OT;
+  static constexpr bool ev = false;
+  static constexpr bool pol = true;
 };
 template <typename OT>
 struct RolloutArgs<ObsEv<OT>> : RolloutArgs<OT> {
   int32_t* hit_out;  // [E, N], or [K, E, N] with traj (last: the fields before it keep their offsets)
 };
+template <typename OT>
+struct RolloutArgs<ObsPol<OT>> : RolloutArgs<OT> {
+  // noise [K, E, N, 9]: row k decides after step k; logits [E, N, 9], or [K, E, N, 9] with traj
+  PolicyArgs pol;  // (last: the fields before it keep their offsets)
+};
+// One lane's decision after step k of a policy rollout: row `row` of the step's obs, noise row k,
+// the logits into the step's output row kr
+template <typename OT>
+__device__ __forceinline__ void policy_act_row(const PolicyArgs& M, int od, const OT* __restrict__ obs, size_t row,
+                                               size_t k, size_t kr, size_t EN, uint8_t* __restrict__ pol_out) {
+  policy_mlp_row<OT>(M, od, obs + row * od, M.noise ? M.noise + (k * EN + row) * kPolicyLogits : nullptr,
+                     pol_out + row * 3, M.logits ? M.logits + (kr * EN + row) * kPolicyLogits : nullptr);
+}
 // Carried Flock rollouts (CARRY) only: this bit of RolloutArgs::cur is MACM_DEBUG_ROLLOUT_RELOAD, every
 // step loads its state and waits for the stores of the step before, as a rollout without the carry.
 // (Not a field of its own: the argument layout of the other rollout kernels stays the measured one.)
@@ -2835,7 +2862,9 @@ template <int MODE, int NCAP, typename OTA, bool SCAL = false, bool CARRY = fals
 __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env_rollout_w64(RolloutArgs<OTA> A0) {
   using OT = typename ObsTag<OTA>::type;
   constexpr bool EV = ObsTag<OTA>::ev;
+  constexpr bool POL = ObsTag<OTA>::pol;
   static_assert(!EV || MODE == kTdm, "combat events are TDM's");
+  static_assert(!POL || (MODE == kFlock && !CARRY), "the MLP policy acts in Flock's closed loop");
   const int nsteps = A0.nsteps;
   const bool bal = A0.B.sched && nsteps >= kRollBalanceMinSteps;  // as in launch_roll
   // TDM tail observation: blocks beyond the envs only observe (TailObs)
@@ -2921,7 +2950,9 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
         uint8_t* const pol_out = A.traj ? pol_in + EN * abytes : pol_in;
         if (lane < N) {
           const size_t row = (size_t)env * N + lane;
-          if constexpr (MODE == kTdm)
+          if constexpr (POL)
+            policy_act_row<OT>(A.pol, (int)od, obs, row, (size_t)k, kr, EN, pol_out);
+          else if constexpr (MODE == kTdm)
             bot_combat_row(obs + row * (N - 1) * 4, TB.mask_out + row * (N - 1), N, pol_out + row * 4);
           else
             bot_flock_row(obs + row * od, (int)od, pol_out + row * 3);
@@ -2982,7 +3013,8 @@ static void launch_roll(int nsteps, unsigned long long astride, int traj, hipStr
                         void* obs, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done,
                         unsigned long long* tail_ctl = nullptr, unsigned tail_tag = 0u, int tail_workers = 0,
                         int tail_k0 = 0, int reload = 0,  // reload: bit 0 MACM_DEBUG_ROLLOUT_RELOAD, bit 1 _NEAR_PLAIN
-                        int32_t* hit_out = nullptr) {     // TDM: non-NULL, the kernel that records the events
+                        int32_t* hit_out = nullptr,       // TDM: non-NULL, the kernel that records the events
+                        const PolicyArgs* policy = nullptr) {  // Flock closed loop: non-NULL, the MLP where the bot is
   // astride == 0: closed loop, `actions` is the bots' action buffer (macm_world_rollout_bots)
   uint8_t* pol = astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(actions)) : nullptr;
   const bool bal = B.sched && nsteps >= kRollBalanceMinSteps;
@@ -3005,6 +3037,13 @@ static void launch_roll(int nsteps, unsigned long long astride, int traj, hipStr
       return;
     }
     if (NCAP == 64 && (reload & 2)) A.cur |= kRollNearPlainBit;
+    if (policy) {
+      RolloutArgs<ObsPol<OT>> R;
+      static_cast<RolloutArgs<OT>&>(R) = A;
+      R.pol = *policy;
+      hipLaunchKernelGGL((env_rollout_w64<kFlock, NCAP, ObsPol<OT>, SCAL>), dim3(blocks), dim3(W), 0, s, R);
+      return;
+    }
   } else if (hit_out) {
     RolloutArgs<ObsEv<OT>> R;
     static_cast<RolloutArgs<OT>&>(R) = A;
@@ -3025,27 +3064,27 @@ hipError_t launch_env_order(const uint32_t* ccount, uint32_t* order, int E, int 
 
 hipError_t launch_rollout_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
                               bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
-                              int nsteps, unsigned long long astride, int traj, int reload) {
+                              int nsteps, unsigned long long astride, int traj, int reload, const PolicyArgs* policy) {
   const TdmParams TP{};
   const TdmBuffers TB{};
   const bool small = P.n_agents <= 32;
   if (obs_f64) {
     if (small)
       launch_roll<kFlock, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                     nullptr, 0u, 0, 0, reload);
+                                     nullptr, 0u, 0, 0, reload, nullptr, policy);
     else
       launch_roll<kFlock, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                     nullptr, 0u, 0, 0, reload);
+                                     nullptr, 0u, 0, 0, reload, nullptr, policy);
   } else {
     if (small)
       launch_roll<kFlock, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                     nullptr, 0u, 0, 0, reload);
+                                     nullptr, 0u, 0, 0, reload, nullptr, policy);
     else if (P.n_envs >= kScalarSweepMinEnvs)
       launch_roll<kFlock, 64, float, true>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll,
-                                           done, nullptr, 0u, 0, 0, reload);
+                                           done, nullptr, 0u, 0, 0, reload, nullptr, policy);
     else
       launch_roll<kFlock, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                     nullptr, 0u, 0, 0, reload);
+                                     nullptr, 0u, 0, 0, reload, nullptr, policy);
   }
   return hipGetLastError();
 }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "flock_common.hpp"
+#include "policy_mlp.hpp"
 #include "py_mt19937.hpp"
 #include "reward_threshold.h"
 
@@ -21,7 +22,8 @@ hipError_t launch_step_w64(const StepParams& P, const WorldBuffers& B, int cur, 
                            bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s);
 hipError_t launch_rollout_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
                               bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
-                              int nsteps, unsigned long long astride, int traj, int reload);
+                              int nsteps, unsigned long long astride, int traj, int reload,
+                              const PolicyArgs* policy = nullptr);
 hipError_t launch_init_w64(const StepParams& P, const WorldBuffers& B, int cur, void* obs, bool obs_f64,
                            int32_t* nbr, const uint8_t* mask, hipStream_t s);
 hipError_t launch_observe_w64(const StepParams& P, const WorldBuffers& B, void* obs, bool obs_f64, int32_t* nbr,
@@ -46,7 +48,7 @@ int tdm_rollout_resident_blocks(int n_agents, bool obs_f64);
 hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
                                  bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
                                  int nsteps, unsigned long long astride, int traj, int reload, uint32_t* mt,
-                                 const PoseDraw& D, const FinalOut& F);
+                                 const PoseDraw& D, const FinalOut& F, const PolicyArgs* policy = nullptr);
 hipError_t launch_tdm_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                      const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
                                      uint8_t* done, hipStream_t s, int nsteps, unsigned long long astride, int traj,
@@ -113,6 +115,8 @@ struct macm_world {
   bool mt_valid = false;
   bool autoreset = false;     // macm_world_set_autoreset: step and rollouts restart the envs that end
   FinalOut fin{};             // macm_world_set_final_outputs: the caller's buffers, kept until replaced or cleared
+  // macm_world_set_policy: the caller's params buffer, kept until replaced or cleared (params NULL: none)
+  macm_policy_mlp policy{0, 0, 0, 0, nullptr};
   uint32_t* hstat = nullptr;  // host-mapped status word (B.host_status is its device alias)
   unsigned long long* bad = nullptr;  // validate_actions: first failing row (device scratch)
   // workgroup-path rollouts: env slices on streams of their own (created on first use)
@@ -937,13 +941,16 @@ static int rollout_wg_slices(macm_world* w, int S, const unsigned char* actions,
   return rc;
 }
 
-// macm_world_rollout / _traj (bots = false) and macm_world_rollout_bots / _traj (bots = true)
+// macm_world_rollout / _traj (bots = false) and macm_world_rollout_bots / _traj (bots = true);
+// macm_world_rollout_policy / _traj: the closed loop of bots = true with the registered policy as the
+// actor (pol: its params and this call's noise and logits; NULL: the scripted bot)
 static int world_rollout(macm_world* w, const void* actions, int n_steps, const macm_outputs* out, void* stream,
-                         bool bots, bool traj) {
+                         bool bots, bool traj, const PolicyArgs* pol = nullptr) {
   if (n_steps < 0) return fail(MACM_E_INVALID, "n_steps must be >= 0");
   if (n_steps == 0) return MACM_OK;  // nothing is read, so actions may be NULL (an empty tensor)
   if (!w || !actions || !out || !out->reward) return fail(MACM_E_INVALID, "world/actions/out/reward is NULL");
-  if (bots && !out->obs) return fail(MACM_E_INVALID, "out->obs is NULL (the bots act on it)");
+  if (bots && !out->obs)
+    return fail(MACM_E_INVALID, pol ? "out->obs is NULL (the policy acts on it)" : "out->obs is NULL (the bots act on it)");
   if (bots && w->cfg.action_mode != MACM_ACTION_DISCRETE) return fail(MACM_E_INVALID, "bots.flock acts in discrete mode");
   if (w->autoreset && !w->mt_valid) return fail(MACM_E_INVALID, kNoStreams);
   if (const int rc = final_outputs_need(w->autoreset, w->fin, out->obs, out->nbr_id, nullptr)) return rc;
@@ -964,15 +971,16 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
     if (w->autoreset)  // the kernels with the in-launch reset
       HIP_TRY(launch_rollout_ar_w64(w->P, w->B, w->cur, actions, out->obs, w->cfg.obs_f64 != 0, out->nbr_id,
                                     out->reward, out->collided, out->done, s, n_steps, astride, traj ? 1 : 0,
-                                    w->roll_reload, w->mt, world_pose_draw(w), w->fin));
+                                    w->roll_reload, w->mt, world_pose_draw(w), w->fin, pol));
     else
       HIP_TRY(launch_rollout_w64(w->P, w->B, w->cur, actions, out->obs, w->cfg.obs_f64 != 0, out->nbr_id, out->reward,
-                                 out->collided, out->done, s, n_steps, astride, traj ? 1 : 0, w->roll_reload));
+                                 out->collided, out->done, s, n_steps, astride, traj ? 1 : 0, w->roll_reload, pol));
     if (n_steps & 1) w->cur ^= 1;
     return MACM_OK;
   }
   const unsigned char* act = static_cast<const unsigned char*>(actions);
-  if (const int S = wg_rollout_slices(w)) return rollout_wg_slices(w, S, act, n_steps, astride, out, traj, s);
+  if (!pol)  // (the policy loop: one stream, no env slices)
+    if (const int S = wg_rollout_slices(w)) return rollout_wg_slices(w, S, act, n_steps, astride, out, traj, s);
   // workgroup path: its three launches per step (and the bot's), in order
   const long long rows = (long long)w->P.n_envs * w->P.n_agents;
   const unsigned long long kstride = bots ? (traj ? (unsigned long long)rows * 3 : 0ull) : astride;
@@ -985,7 +993,7 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
     else
       HIP_TRY(launch_step_wg(w->P, w->B, w->cur, w->tcap, act_k, ok.obs, w->cfg.obs_f64 != 0, ok.nbr_id, ok.reward,
                              ok.collided, ok.done, s, handoff_for(w),
-                             bots ? const_cast<unsigned char*>(act_k) + (traj ? rows * 3 : 0) : nullptr));
+                             bots && !pol ? const_cast<unsigned char*>(act_k) + (traj ? rows * 3 : 0) : nullptr));
     w->cur ^= 1;
     if (w->autoreset) {
       const int rc = world_autoreset_step(w, &ok, s);
@@ -993,9 +1001,16 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
     }
     // autoreset: kernel C's fused bot acted on the terminal observation; the bots launch over every
     // row takes a reset env's next actions from its new initial obs (the other rows: the same actions)
-    if (bots && (w->big || w->autoreset))
+    if (bots && !pol && (w->big || w->autoreset))
       HIP_TRY(launch_bots_flock(ok.obs, w->cfg.obs_f64 != 0, obs_dim(w->cfg), rows,
                                 const_cast<unsigned char*>(act_k) + (traj ? rows * 3 : 0), s));
+    if (pol) {  // the policy over every row: noise row k, the logits into the step's output row
+      PolicyArgs M = *pol;
+      if (M.noise) M.noise += (size_t)k * rows * kPolicyLogits;
+      if (M.logits && traj) M.logits += (size_t)k * rows * kPolicyLogits;
+      HIP_TRY(launch_policy_flock(M, ok.obs, w->cfg.obs_f64 != 0, obs_dim(w->cfg), rows,
+                                  const_cast<unsigned char*>(act_k) + (traj ? rows * 3 : 0), s));
+    }
   }
   return MACM_OK;
 }
@@ -1016,6 +1031,64 @@ int macm_world_rollout_bots(macm_world* w, uint8_t* actions, int n_steps, const 
 int macm_world_rollout_bots_traj(macm_world* w, uint8_t* actions, int n_steps, const macm_outputs* traj,
                                  void* stream) {
   return world_rollout(w, actions, n_steps, traj, stream, true, true);
+}
+
+// A policy struct as the kernels can take it: shapes from the supported sets, params set and aligned
+static int policy_check(const macm_policy_mlp* p) {
+  if (p->in_dim != 4 && p->in_dim != 6) return fail(MACM_E_INVALID, "policy: in_dim must be 4 (polar) or 6 (cartesian)");
+  if (p->hidden != 16 && p->hidden != 32) return fail(MACM_E_INVALID, "policy: hidden must be 16 or 32");
+  if (p->n_hidden != 1 && p->n_hidden != 2) return fail(MACM_E_INVALID, "policy: n_hidden must be 1 or 2");
+  if (p->reserved != 0) return fail(MACM_E_INVALID, "policy: reserved must be 0");
+  if (!p->params) return fail(MACM_E_INVALID, "policy: params is NULL");
+  if (reinterpret_cast<uintptr_t>(p->params) & 15) return fail(MACM_E_INVALID, "policy: params must be 16-byte aligned");
+  return MACM_OK;
+}
+
+int macm_policy_flock(const macm_policy_mlp* p, const void* obs, int32_t obs_f64, int64_t rows, const float* noise,
+                      uint8_t* actions, float* logits, void* stream) {
+  if (!p) return fail(MACM_E_INVALID, "policy is NULL");
+  if (const int rc = policy_check(p)) return rc;
+  if (!obs || !actions) return fail(MACM_E_INVALID, "obs/actions is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "rows must be >= 0");
+  const PolicyArgs M{p->params, noise, logits, p->hidden, p->n_hidden};
+  HIP_TRY(launch_policy_flock(M, obs, obs_f64 != 0, p->in_dim, rows, actions, (hipStream_t)stream));
+  return MACM_OK;
+}
+
+int macm_world_set_policy(macm_world* w, const macm_policy_mlp* p) {
+  if (!w) return fail(MACM_E_INVALID, "world is NULL");
+  if (!p) {
+    w->policy = macm_policy_mlp{0, 0, 0, 0, nullptr};
+    return MACM_OK;
+  }
+  if (const int rc = policy_check(p)) return rc;
+  if (w->cfg.action_mode != MACM_ACTION_DISCRETE)
+    return fail(MACM_E_UNSUPPORTED, "policy: the MLP policy acts in discrete mode (MultiDiscrete([3, 3, 3]))");
+  if (p->in_dim != obs_dim(w->cfg))
+    return fail(MACM_E_INVALID, "policy: in_dim " + std::to_string(p->in_dim) + " is not the world's obs_dim " +
+                                    std::to_string(obs_dim(w->cfg)));
+  w->policy = *p;
+  return MACM_OK;
+}
+
+static int world_rollout_policy(macm_world* w, uint8_t* actions, int n_steps, const float* noise, float* logits,
+                                const macm_outputs* out, void* stream, bool traj) {
+  if (n_steps < 0) return fail(MACM_E_INVALID, "n_steps must be >= 0");
+  if (n_steps == 0) return MACM_OK;
+  if (!w) return fail(MACM_E_INVALID, "world is NULL");
+  if (!w->policy.params) return fail(MACM_E_INVALID, "no policy is registered (macm_world_set_policy)");
+  const PolicyArgs M{w->policy.params, noise, logits, w->policy.hidden, w->policy.n_hidden};
+  return world_rollout(w, actions, n_steps, out, stream, true, traj, &M);
+}
+
+int macm_world_rollout_policy(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise, float* logits,
+                              const macm_outputs* out, void* stream) {
+  return world_rollout_policy(w, actions, n_steps, noise, logits, out, stream, false);
+}
+
+int macm_world_rollout_policy_traj(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise, float* logits,
+                                   const macm_outputs* traj, void* stream) {
+  return world_rollout_policy(w, actions, n_steps, noise, logits, traj, stream, true);
 }
 
 int macm_world_observe(macm_world* w, const macm_outputs* out, void* stream) {

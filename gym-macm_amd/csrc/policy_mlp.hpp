@@ -1,0 +1,118 @@
+// policy_mlp.hpp — one agent's decision of a learned policy: a float32 MLP over the agent's obs row,
+// shared by the one-shot kernel (policy.hip, macm_policy_flock) and the closed-loop rollouts
+// (flock_step_w64.hip / rollout_autoreset.inc, macm_world_rollout_policy), where it stands in the
+// place of the scripted bot (bots.hpp).
+//
+// The definition (include/macm.h, macm_policy_mlp), all float32:
+//   x[q]  = (float)obs[q], q < OD (a float64 obs rounds to nearest)
+//   layer : acc = b[j]; acc = fmaf(W[k][j], x[k], acc) for k ascending; one rounding per step
+//   hidden: relu(v) = v > 0 ? v : +0.0f (so -0 and NaN give +0); the output layer has none
+//   head h: z[c] = logits[3h + c] (+ noise[3h + c]); action[h] = the lowest c with the largest z,
+//           by `z[c] > best` from best = -inf, so a NaN is never chosen over a number
+// lane = row: every weight is a wave-uniform operand. The params are read through the constant
+// address space, so the compiler fetches them with scalar loads (1,545 floats at most: they stay
+// in the scalar cache) and each v_fma_f32 takes its weight from an SGPR; the result is already in
+// the lane that stores the action. Nothing here uses LDS. -ffp-contract=off (hipflags.mk) leaves
+// the explicit fmaf calls alone and keeps the noise add a separate rounding.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace macm {
+
+constexpr int kPolicyLogits = 9;  // MultiDiscrete([3, 3, 3]): head h at logits[3h + c]
+
+// What the kernels take of a registered policy and of one rollout call (device pointers)
+struct PolicyArgs {
+  const float* params;  // W1[OD][H], b1[H], (W2[H][H], b2[H]), W3[H][9], b3[9]; 16-byte aligned
+  const float* noise;   // [rows, 9] or NULL
+  float* logits;        // [rows, 9] or NULL
+  int32_t hidden;       // H: 16 or 32
+  int32_t n_hidden;     // 1 or 2
+};
+
+using policy_cptr = const __attribute__((address_space(4))) float*;
+
+// y[j] = b[j] + sum_k W[k][j] x[k] as the k-ordered fmaf chain; W, b wave-uniform
+template <int IN, int OUT, bool RELU>
+__device__ __forceinline__ void policy_layer(policy_cptr W, policy_cptr b, const float (&x)[IN], float (&y)[OUT]) {
+#pragma unroll
+  for (int j = 0; j < OUT; ++j) y[j] = b[j];
+#pragma unroll
+  for (int k = 0; k < IN; ++k) {
+#pragma unroll
+    for (int j = 0; j < OUT; ++j) y[j] = __builtin_fmaf(W[k * OUT + j], x[k], y[j]);
+  }
+  if constexpr (RELU) {
+#pragma unroll
+    for (int j = 0; j < OUT; ++j) y[j] = y[j] > 0.0f ? y[j] : 0.0f;
+  }
+}
+
+template <typename OT, int OD, int H>
+__device__ __forceinline__ void policy_mlp_row_t(policy_cptr p, int n_hidden, const OT* __restrict__ o,
+                                                 const float* __restrict__ noise, uint8_t* __restrict__ act,
+                                                 float* __restrict__ logits) {
+  float x[OD];
+#pragma unroll
+  for (int q = 0; q < OD; ++q) x[q] = (float)o[q];
+  float h[H];
+  policy_layer<OD, H, true>(p, p + OD * H, x, h);
+  p += OD * H + H;
+  if (n_hidden == 2) {  // wave-uniform
+    float g[H];
+    policy_layer<H, H, true>(p, p + H * H, h, g);
+#pragma unroll
+    for (int j = 0; j < H; ++j) h[j] = g[j];
+    p += H * H + H;
+  }
+  float y[kPolicyLogits];
+  policy_layer<H, kPolicyLogits, false>(p, p + H * kPolicyLogits, h, y);
+  if (logits) {
+#pragma unroll
+    for (int j = 0; j < kPolicyLogits; ++j) logits[j] = y[j];
+  }
+  if (noise) {
+#pragma unroll
+    for (int j = 0; j < kPolicyLogits; ++j) y[j] = y[j] + noise[j];
+  }
+#pragma unroll
+  for (int hd = 0; hd < 3; ++hd) {
+    int best = 0;
+    float bz = -__builtin_inff();
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (y[3 * hd + c] > bz) {
+        best = c;
+        bz = y[3 * hd + c];
+      }
+    }
+    act[hd] = (uint8_t)best;
+  }
+}
+
+// o: the agent's obs row (od = 4 polar / 6 cartesian) as stored; noise / logits: its 9 floats or NULL;
+// act: its 3 action bytes. M.params, M.hidden and M.n_hidden must be wave-uniform.
+template <typename OT>
+__device__ __forceinline__ void policy_mlp_row(const PolicyArgs& M, int od, const OT* __restrict__ o,
+                                               const float* __restrict__ noise, uint8_t* __restrict__ act,
+                                               float* __restrict__ logits) {
+  const policy_cptr p = (policy_cptr)(unsigned long long)M.params;
+  if (od == 6) {
+    if (M.hidden == 32)
+      policy_mlp_row_t<OT, 6, 32>(p, M.n_hidden, o, noise, act, logits);
+    else
+      policy_mlp_row_t<OT, 6, 16>(p, M.n_hidden, o, noise, act, logits);
+  } else {
+    if (M.hidden == 32)
+      policy_mlp_row_t<OT, 4, 32>(p, M.n_hidden, o, noise, act, logits);
+    else
+      policy_mlp_row_t<OT, 4, 16>(p, M.n_hidden, o, noise, act, logits);
+  }
+}
+
+// host side (C++ linkage, macm_capi.hip): the one-shot kernel over rows (policy.hip)
+hipError_t launch_policy_flock(const PolicyArgs& M, const void* obs, bool obs_f64, int od, long long rows,
+                               uint8_t* act, hipStream_t s);
+
+}  // namespace macm

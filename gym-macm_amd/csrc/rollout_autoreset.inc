@@ -195,6 +195,12 @@ struct RolloutArArgs<ObsEv<OT>> : RolloutArArgs<OT> {
   int32_t* hit_out;  // [E, N], or [K, E, N] with A.traj
 };
 
+// a registered policy (ObsPol): likewise, the policy's fields follow
+template <typename OT>
+struct RolloutArArgs<ObsPol<OT>> : RolloutArArgs<OT> {
+  PolicyArgs pol;  // noise [K, E, N, 9], logits [E, N, 9] or [K, E, N, 9] with A.traj
+};
+
 // env_rollout_w64 with the in-launch reset; no tail or split observation (their pose snapshots know
 // nothing of a mid-launch respawn: TDM observes inside the step).
 // OTA: OT or ObsEv<OT>, as env_rollout_w64. The step writes the events, the in-launch reset none: it
@@ -203,7 +209,9 @@ template <int MODE, int NCAP, typename OTA, bool SCAL = false, bool CARRY = fals
 __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env_rollout_ar_w64(RolloutArArgs<OTA> R0) {
   using OT = typename ObsTag<OTA>::type;
   constexpr bool EV = ObsTag<OTA>::ev;
+  constexpr bool POL = ObsTag<OTA>::pol;
   static_assert(!EV || MODE == kTdm, "combat events are TDM's");
+  static_assert(!POL || (MODE == kFlock && !CARRY), "the MLP policy acts in Flock's closed loop");
   const int nsteps = R0.A.nsteps;
   const bool bal = R0.A.B.sched && nsteps >= kRollBalanceMinSteps;  // as in launch_roll_ar
   const int env = bal ? (int)R0.A.B.sched[R0.A.sched_off + blockIdx.x] : (int)blockIdx.x;
@@ -284,7 +292,9 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
         uint8_t* const pol_out = A.traj ? pol_in + EN * abytes : pol_in;
         if (lane < N) {
           const size_t row = (size_t)env * N + lane;
-          if constexpr (MODE == kTdm)
+          if constexpr (POL)
+            policy_act_row<OT>(R.pol, (int)od, obs, row, (size_t)k, kr, EN, pol_out);
+          else if constexpr (MODE == kTdm)
             bot_combat_row(obs + row * (N - 1) * 4, TB.mask_out + row * (N - 1), N, pol_out + row * 4);
           else
             bot_flock_row(obs + row * od, (int)od, pol_out + row * 3);
@@ -302,7 +312,8 @@ template <int MODE, int NCAP, typename OT, bool SCAL = false>
 static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hipStream_t s, const StepParams& P,
                            const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur, const void* actions,
                            void* obs, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, int reload, uint32_t* mt,
-                           const PoseDraw& D, const FinalOut& F, int32_t* hit_out = nullptr) {
+                           const PoseDraw& D, const FinalOut& F, int32_t* hit_out = nullptr,
+                           const PolicyArgs* policy = nullptr) {
   // astride == 0: closed loop, `actions` is the bots' action buffer
   uint8_t* pol = astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(actions)) : nullptr;
   if (B.sched && nsteps >= kRollBalanceMinSteps) {  // the balanced env order, as launch_roll
@@ -323,6 +334,13 @@ static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hip
       return;
     }
     if (NCAP == 64 && (reload & 2)) R.A.cur |= kRollNearPlainBit;
+    if (policy) {  // a registered policy: the kernel with the MLP where the bot is
+      RolloutArArgs<ObsPol<OT>> V;
+      static_cast<RolloutArArgs<OT>&>(V) = R;
+      V.pol = *policy;
+      hipLaunchKernelGGL((env_rollout_ar_w64<kFlock, NCAP, ObsPol<OT>, SCAL>), dim3(P.n_envs), dim3(W), 0, s, V);
+      return;
+    }
   } else if (hit_out) {  // events registered: the kernel that records them
     RolloutArArgs<ObsEv<OT>> V;
     static_cast<RolloutArArgs<OT>&>(V) = R;
@@ -337,27 +355,27 @@ static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hip
 hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
                                  bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
                                  int nsteps, unsigned long long astride, int traj, int reload, uint32_t* mt,
-                                 const PoseDraw& D, const FinalOut& F) {
+                                 const PoseDraw& D, const FinalOut& F, const PolicyArgs* policy) {
   const TdmParams TP{};
   const TdmBuffers TB{};
   const bool small = P.n_agents <= 32;
   if (obs_f64) {
     if (small)
       launch_roll_ar<kFlock, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                        reload, mt, D, F);
+                                        reload, mt, D, F, nullptr, policy);
     else
       launch_roll_ar<kFlock, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                        reload, mt, D, F);
+                                        reload, mt, D, F, nullptr, policy);
   } else {
     if (small)
       launch_roll_ar<kFlock, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                       reload, mt, D, F);
+                                       reload, mt, D, F, nullptr, policy);
     else if (P.n_envs >= kScalarSweepMinEnvs)
       launch_roll_ar<kFlock, 64, float, true>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll,
-                                             done, reload, mt, D, F);
+                                             done, reload, mt, D, F, nullptr, policy);
     else
       launch_roll_ar<kFlock, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                       reload, mt, D, F);
+                                       reload, mt, D, F, nullptr, policy);
   }
   return hipGetLastError();
 }

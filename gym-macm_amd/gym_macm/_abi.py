@@ -82,6 +82,13 @@ class MacmTdmEvents(Structure):
     _fields_ = [("hit_id", c_void_p), ("rows", c_int32)]
 
 
+class MacmPolicyMlp(Structure):
+    """macm_policy_mlp: a float32 MLP policy over Flock obs rows; params is a device pointer to
+    W1[in][hidden], b1, (W2[hidden][hidden], b2), W3[hidden][9], b3, 16-byte aligned."""
+    _fields_ = [("in_dim", c_int32), ("hidden", c_int32), ("n_hidden", c_int32), ("reserved", c_int32),
+                ("params", c_void_p)]
+
+
 class MacmState(Structure):
     _fields_ = [(n, c_void_p) for n in (
         "pos", "vel", "angle", "fat", "sleep", "targets", "contact_count", "contact_ab",
@@ -250,6 +257,13 @@ SIGNATURES = {
     "macm_tdm_launch_flags": (c_int, [c_void_p]),
     "macm_tdm_reserve": (c_int, [c_void_p, c_int32, c_void_p]),
     "macm_tdm_set_debug": (c_int, [c_void_p, c_int32]),
+    "macm_policy_flock": (c_int, [POINTER(MacmPolicyMlp), c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
+    "macm_world_set_policy": (c_int, [c_void_p, POINTER(MacmPolicyMlp)]),
+    "macm_world_rollout_policy": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, POINTER(MacmOutputs),
+                                          c_void_p]),
+    "macm_world_rollout_policy_traj": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, POINTER(MacmOutputs),
+                                               c_void_p]),
     "macm_bots_flock": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
     "macm_bots_combat": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
 }

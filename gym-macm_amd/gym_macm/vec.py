@@ -122,6 +122,17 @@ class FlockVec(object):
             return self.world.rollout_bots_traj(actions, n_steps, traj)
         return self.world.rollout_bots(actions, n_steps)
 
+    def set_policy(self, policy) -> None:
+        """Register the actor of rollout_policy: a gym_macm.policy.MlpPolicy, or None (World.set_policy)."""
+        self.world.set_policy(policy)
+
+    def rollout_policy(self, actions, n_steps, noise=None, trajectory=False, traj=None, logits=None):
+        """n_steps of the closed loop step -> policy -> step in one launch, beside rollout_bots: the
+        registered MlpPolicy acts on the observation each step wrote (World.rollout_policy). ``noise``
+        [n_steps, E, N, 9] samples (None: argmax); ``logits`` keeps what the policy computed. With
+        ``autoreset`` an env that ends restarts inside the launch and acts on its new initial obs."""
+        return self.world.rollout_policy(actions, n_steps, noise=noise, trajectory=trajectory, traj=traj, logits=logits)
+
     def reset_envs(self, mask=None):
         """New episodes in the masked envs (see World.reset_envs)."""
         return self.world.reset_envs(mask)

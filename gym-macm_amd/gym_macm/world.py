@@ -111,6 +111,7 @@ class World:
                                      _ptr(self.done))
         self._out_obs = _abi.MacmOutputs(_ptr(self.obs), _ptr(self.nbr_id), None, None, None)
         self.final_obs = self.final_nbr_id = self.final_length = self.final_ends = None  # set_final_outputs
+        self.policy = None  # set_policy
 
     def __del__(self):
         h = getattr(self, "h", None)
@@ -333,6 +334,59 @@ class World:
     def rollout_bots_raw(self, actions_ptr: int, n_steps: int, stream_handle: int) -> None:
         self.L.macm_world_rollout_bots(self.h, ctypes.c_void_p(actions_ptr), int(n_steps), ctypes.byref(self._out),
                                        ctypes.c_void_p(stream_handle))
+
+    def set_policy(self, policy) -> None:
+        """Register the actor of rollout_policy (macm_world_set_policy): a gym_macm.policy.MlpPolicy,
+        or None to clear. The library reads ``policy.params`` at every launch, so values written into
+        it in place between two launches are followed; this object keeps the policy alive."""
+        if policy is None:
+            _abi.check(self.L.macm_world_set_policy(self.h, None), "macm_world_set_policy")
+            self.policy = None
+            return
+        if policy.device != self.device:
+            raise ValueError(f"the policy's params must be on {self.device}")
+        _abi.check(self.L.macm_world_set_policy(self.h, ctypes.byref(policy.struct())), "macm_world_set_policy")
+        self.policy = policy
+
+    def rollout_policy(self, actions: torch.Tensor, n_steps: int, noise: torch.Tensor = None, trajectory: bool = False,
+                       traj: dict = None, logits: torch.Tensor = None):
+        """n_steps of the closed loop step -> policy -> step with the registered policy as the actor,
+        one launch on the wave path (macm_world_rollout_policy / _traj), as rollout_bots is for the bot.
+        actions: uint8 [E, N, 3], the first step's on entry (``policy.act(self.obs)``) and the next on
+        return; with ``trajectory`` [n_steps + 1, E, N, 3], row 0 given and step k writing row k + 1.
+        noise: float32 [n_steps, E, N, 9] or None (argmax); row k decides after step k.
+        logits: float32 [E, N, 9] (the last step's remain), with ``trajectory`` [n_steps, E, N, 9], or
+        None; row k holds the logits computed from obs row k.
+        Returns (obs, nbr_id, reward, done), or with ``trajectory`` the dict of rollout_traj()."""
+        K, E, N = int(n_steps), self.E, self.N
+        ashape = (K + 1, E, N, 3) if trajectory else (E, N, 3)
+        if (actions.device != self.device or not actions.is_contiguous() or actions.dtype != torch.uint8
+                or tuple(actions.shape) != ashape):
+            raise ValueError(f"actions must be a contiguous uint8 {list(ashape)} tensor on the world's device")
+        for name, t, shp in (("noise", noise, (K, E, N, 9)), ("logits", logits, (K, E, N, 9) if trajectory else (E, N, 9))):
+            if t is not None and (t.device != self.device or not t.is_contiguous() or t.dtype != torch.float32
+                                  or tuple(t.shape) != shp):
+                raise ValueError(f"{name} must be a contiguous float32 {list(shp)} tensor on the world's device")
+        if not trajectory:
+            _abi.check(self.L.macm_world_rollout_policy(self.h, _ptr(actions), K, _ptr(noise), _ptr(logits),
+                                                        ctypes.byref(self._out), self._stream()),
+                       "macm_world_rollout_policy")
+            return self.obs, self.nbr_id, self.reward, self.done
+        traj = self.trajectory_buffers(K) if traj is None else traj
+        out = self._traj_out(traj, K)
+        _abi.check(self.L.macm_world_rollout_policy_traj(self.h, _ptr(actions), K, _ptr(noise), _ptr(logits),
+                                                         ctypes.byref(out), self._stream()),
+                   "macm_world_rollout_policy_traj")
+        if K > 0:
+            self._keep_last(traj, K)
+        return traj
+
+    def rollout_policy_raw(self, actions_ptr: int, n_steps: int, noise_ptr: int, logits_ptr: int,
+                           stream_handle: int) -> None:
+        """Minimal-overhead policy rollout for timed loops (no validation); 0 = no noise / logits."""
+        self.L.macm_world_rollout_policy(self.h, ctypes.c_void_p(actions_ptr), int(n_steps),
+                                         ctypes.c_void_p(noise_ptr or None), ctypes.c_void_p(logits_ptr or None),
+                                         ctypes.byref(self._out), ctypes.c_void_p(stream_handle))
 
     def observe(self):
         _abi.check(self.L.macm_world_observe(self.h, ctypes.byref(self._out_obs), self._stream()),

@@ -468,6 +468,70 @@ int macm_world_rollout_traj(macm_world* w, const void* actions, int32_t n_steps,
 int macm_world_rollout_bots_traj(macm_world* w, uint8_t* actions, int32_t n_steps, const macm_outputs* traj,
                                  void* stream);
 
+/*
+ * A learned policy as the actor of the closed loop: a float32 MLP over every agent's obs row, in the
+ * place of the scripted bot, so that a collector gets n_steps of (obs, action, logits, reward, done,
+ * final obs) from one launch. Defined so that it can be checked bit for bit; all arithmetic float32:
+ *   input   x[q] = (float)obs[q], q < in_dim, the row as stored (float64 obs round to nearest);
+ *   layer   acc = b[j], then acc = fmaf(W[k][j], x[k], acc) for k = 0, 1, ... ascending: one rounding
+ *           per step, no other association;
+ *   hidden  relu(v) = v > 0 ? v : +0.0f (-0 and NaN give +0); the output layer has no activation;
+ *   output  9 logits, head h in {0, 1, 2} of MultiDiscrete([3, 3, 3]) at logits[3h + c];
+ *   action  z[c] = logits[3h + c] + noise[3h + c] (one float32 add; without noise z[c] = logits[3h + c]);
+ *           action[h] = the lowest c with the largest z: best = 0, top = -inf, then for c = 0, 1, 2
+ *           `if (z[c] > top) best = c, top = z[c]`, so a NaN is never chosen over a number.
+ * Denormals are kept; the sign and payload of a NaN logit are unspecified. The caller supplies the noise (Gumbel noise for sampling; NULL: the argmax) as
+ * it supplies the actions of macm_world_rollout: the device draws nothing and takes no logarithm, and
+ * the learner recomputes log-probabilities from the stored logits.
+ *   params: device float32, 16-byte aligned, row-major [in][out]:
+ *           W1[in_dim][hidden], b1[hidden], (W2[hidden][hidden], b2[hidden] if n_hidden == 2),
+ *           W3[hidden][9], b3[9].
+ * hidden is 16 or 32, n_hidden 1 or 2, in_dim 4 (polar) or 6 (cartesian), reserved 0.
+ * Flock worlds with discrete actions only: a TDM observation is a masked set, not a fixed vector, and
+ * continuous actions have no heads (both out of scope). Additive: MACM_ABI_VERSION stays 9.
+ */
+typedef struct macm_policy_mlp {
+  int32_t in_dim, hidden, n_hidden, reserved;
+  const float* params;
+} macm_policy_mlp;
+
+/*
+ * The policy's decision for `rows` obs rows ([rows, in_dim], float32 or float64 as obs_f64), as
+ * macm_bots_flock is for the bot: the first actions of a closed loop from the initial obs, and what
+ * the per-step loop calls. noise [rows, 9] or NULL; actions uint8 [rows, 3]; logits [rows, 9] or NULL.
+ * MACM_E_INVALID: p NULL or outside the shapes above, params NULL or misaligned, obs or actions NULL.
+ */
+int macm_policy_flock(const macm_policy_mlp* p, const void* obs, int32_t obs_f64, int64_t rows, const float* noise,
+                      uint8_t* actions, float* logits, void* stream);
+
+/*
+ * Registers the policy of macm_world_rollout_policy. A registration, as macm_world_set_final_outputs:
+ * the world keeps a copy of the struct, not of the params buffer, until it is replaced, cleared (p
+ * NULL) or the world is destroyed; the learner may overwrite params between launches, and the next
+ * launch reads the new values. MACM_E_INVALID, nothing changed: a NULL world, a struct outside the
+ * shapes above, params NULL or misaligned, in_dim other than the world's obs_dim.
+ * MACM_E_UNSUPPORTED: a continuous-action world.
+ */
+int macm_world_set_policy(macm_world* w, const macm_policy_mlp* p);
+
+/*
+ * n_steps of the closed loop `step -> policy -> step`, as macm_world_rollout_bots / _bots_traj with
+ * the registered policy as the actor: one launch on the wave path (N <= 64); on the other paths the
+ * launches of macm_world_step and macm_policy_flock on the caller's stream (no env slices).
+ *   actions: [E, N, 3] in and out; trajectory form [n_steps + 1, E, N, 3], row 0 given, step k writes row k + 1.
+ *   noise:   [n_steps, E, N, 9] or NULL; row k is used for the decision taken after step k.
+ *   logits:  [E, N, 9] (the last step's remain), trajectory form [n_steps, E, N, 9], or NULL; row k
+ *            holds the logits computed from obs row k.
+ * With autoreset on, a reset env's next action comes from its new initial obs (which is what obs row
+ * k then holds), as for the bots; the final outputs are written as in every other form.
+ * out->obs must be set. MACM_E_INVALID without a registered policy. n_steps = 0 does nothing.
+ * Same results as n_steps of (macm_world_step, macm_policy_flock).
+ */
+int macm_world_rollout_policy(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise, float* logits,
+                              const macm_outputs* out, void* stream);
+int macm_world_rollout_policy_traj(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise,
+                                   float* logits, const macm_outputs* traj, void* stream);
+
 /* Observation of the current state without stepping (Flock.get_obs, mvmnt.py:181-222). */
 int macm_world_observe(macm_world* w, const macm_outputs* out, void* stream);
 
