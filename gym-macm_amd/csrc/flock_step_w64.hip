@@ -2755,23 +2755,38 @@ struct ObsEv {};
 // bot is, and their argument grows by the policy's fields.
 template <typename OT>
 struct ObsPol {};
+// ... and with a critic registered beside the policy (macm_world_rollout_policy_value): ObsPolV<float> /
+// ObsPolV<double>, the ObsPol kernels with the critic of policy_mlp.hpp evaluated where the actor is;
+// their argument grows by the critic's fields after the policy's.
+template <typename OT>
+struct ObsPolV {};
 template <typename OTA>
 struct ObsTag {
   using type = OTA;
   static constexpr bool ev = false;
   static constexpr bool pol = false;
+  static constexpr bool val = false;
 };
 template <typename OT>
 struct ObsTag<ObsEv<OT>> {
   using type = OT;
   static constexpr bool ev = true;
   static constexpr bool pol = false;
+  static constexpr bool val = false;
 };
 template <typename OT>
 struct ObsTag<ObsPol<OT>> {
   using type = OT;
   static constexpr bool ev = false;
   static constexpr bool pol = true;
+  static constexpr bool val = false;
+};
+template <typename OT>
+struct ObsTag<ObsPolV<OT>> {
+  using type = OT;
+  static constexpr bool ev = false;
+  static constexpr bool pol = true;
+  static constexpr bool val = true;
 };
 template <typename OT>
 struct RolloutArgs<ObsEv<OT>> : RolloutArgs<OT> {
@@ -2782,6 +2797,18 @@ struct RolloutArgs<ObsPol<OT>> : RolloutArgs<OT> {
   // noise [K, E, N, 9]: row k decides after step k; logits [E, N, 9], or [K, E, N, 9] with traj
   PolicyArgs pol;  // (last: the fields before it keep their offsets)
 };
+template <typename OT>
+struct RolloutArgs<ObsPolV<OT>> : RolloutArgs<ObsPol<OT>> {
+  // values [E, N], or [K + 1, E, N] with traj: step k writes row k + 1; boot [E, N], or [K, E, N] with traj
+  ValueArgs val;
+};
+// One lane's critic stores of step k of a policy rollout: v is the bootstrap value of the step's output
+// row kr (with_boot) and the value of the obs row the next action is taken from
+__device__ __forceinline__ void value_store_row(const ValueArgs& V, float v, size_t row, size_t k, size_t kr, size_t EN,
+                                                bool traj, bool with_boot) {
+  if (with_boot && V.boot) V.boot[kr * EN + row] = v;
+  if (V.values) V.values[(traj ? k + 1 : 0) * EN + row] = v;
+}
 // One lane's decision after step k of a policy rollout: row `row` of the step's obs, noise row k,
 // the logits into the step's output row kr
 template <typename OT>
@@ -2863,6 +2890,7 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
   using OT = typename ObsTag<OTA>::type;
   constexpr bool EV = ObsTag<OTA>::ev;
   constexpr bool POL = ObsTag<OTA>::pol;
+  constexpr bool VAL = ObsTag<OTA>::val;
   static_assert(!EV || MODE == kTdm, "combat events are TDM's");
   static_assert(!POL || (MODE == kFlock && !CARRY), "the MLP policy acts in Flock's closed loop");
   const int nsteps = A0.nsteps;
@@ -2950,6 +2978,9 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
         uint8_t* const pol_out = A.traj ? pol_in + EN * abytes : pol_in;
         if (lane < N) {
           const size_t row = (size_t)env * N + lane;
+          if constexpr (VAL)  // no reset here: the step's obs row is the row the next action is taken from
+            value_store_row(A.val, value_mlp_row<OT>(A.val, (int)od, obs + row * od), row, (size_t)k, kr, EN, A.traj != 0,
+                            true);
           if constexpr (POL)
             policy_act_row<OT>(A.pol, (int)od, obs, row, (size_t)k, kr, EN, pol_out);
           else if constexpr (MODE == kTdm)
@@ -3014,7 +3045,8 @@ static void launch_roll(int nsteps, unsigned long long astride, int traj, hipStr
                         unsigned long long* tail_ctl = nullptr, unsigned tail_tag = 0u, int tail_workers = 0,
                         int tail_k0 = 0, int reload = 0,  // reload: bit 0 MACM_DEBUG_ROLLOUT_RELOAD, bit 1 _NEAR_PLAIN
                         int32_t* hit_out = nullptr,       // TDM: non-NULL, the kernel that records the events
-                        const PolicyArgs* policy = nullptr) {  // Flock closed loop: non-NULL, the MLP where the bot is
+                        const PolicyArgs* policy = nullptr,    // Flock closed loop: non-NULL, the MLP where the bot is
+                        const ValueArgs* critic = nullptr) {   // with policy: non-NULL, the critic beside it
   // astride == 0: closed loop, `actions` is the bots' action buffer (macm_world_rollout_bots)
   uint8_t* pol = astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(actions)) : nullptr;
   const bool bal = B.sched && nsteps >= kRollBalanceMinSteps;
@@ -3037,6 +3069,14 @@ static void launch_roll(int nsteps, unsigned long long astride, int traj, hipStr
       return;
     }
     if (NCAP == 64 && (reload & 2)) A.cur |= kRollNearPlainBit;
+    if (policy && critic) {
+      RolloutArgs<ObsPolV<OT>> R;
+      static_cast<RolloutArgs<OT>&>(R) = A;
+      R.pol = *policy;
+      R.val = *critic;
+      hipLaunchKernelGGL((env_rollout_w64<kFlock, NCAP, ObsPolV<OT>, SCAL>), dim3(blocks), dim3(W), 0, s, R);
+      return;
+    }
     if (policy) {
       RolloutArgs<ObsPol<OT>> R;
       static_cast<RolloutArgs<OT>&>(R) = A;
@@ -3064,27 +3104,28 @@ hipError_t launch_env_order(const uint32_t* ccount, uint32_t* order, int E, int 
 
 hipError_t launch_rollout_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
                               bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
-                              int nsteps, unsigned long long astride, int traj, int reload, const PolicyArgs* policy) {
+                              int nsteps, unsigned long long astride, int traj, int reload, const PolicyArgs* policy,
+                              const ValueArgs* critic) {
   const TdmParams TP{};
   const TdmBuffers TB{};
   const bool small = P.n_agents <= 32;
   if (obs_f64) {
     if (small)
       launch_roll<kFlock, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                     nullptr, 0u, 0, 0, reload, nullptr, policy);
+                                     nullptr, 0u, 0, 0, reload, nullptr, policy, critic);
     else
       launch_roll<kFlock, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                     nullptr, 0u, 0, 0, reload, nullptr, policy);
+                                     nullptr, 0u, 0, 0, reload, nullptr, policy, critic);
   } else {
     if (small)
       launch_roll<kFlock, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                     nullptr, 0u, 0, 0, reload, nullptr, policy);
+                                     nullptr, 0u, 0, 0, reload, nullptr, policy, critic);
     else if (P.n_envs >= kScalarSweepMinEnvs)
       launch_roll<kFlock, 64, float, true>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll,
-                                           done, nullptr, 0u, 0, 0, reload, nullptr, policy);
+                                           done, nullptr, 0u, 0, 0, reload, nullptr, policy, critic);
     else
       launch_roll<kFlock, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                     nullptr, 0u, 0, 0, reload, nullptr, policy);
+                                     nullptr, 0u, 0, 0, reload, nullptr, policy, critic);
   }
   return hipGetLastError();
 }

@@ -23,7 +23,7 @@ hipError_t launch_step_w64(const StepParams& P, const WorldBuffers& B, int cur, 
 hipError_t launch_rollout_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
                               bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
                               int nsteps, unsigned long long astride, int traj, int reload,
-                              const PolicyArgs* policy = nullptr);
+                              const PolicyArgs* policy = nullptr, const ValueArgs* critic = nullptr);
 hipError_t launch_init_w64(const StepParams& P, const WorldBuffers& B, int cur, void* obs, bool obs_f64,
                            int32_t* nbr, const uint8_t* mask, hipStream_t s);
 hipError_t launch_observe_w64(const StepParams& P, const WorldBuffers& B, void* obs, bool obs_f64, int32_t* nbr,
@@ -48,7 +48,8 @@ int tdm_rollout_resident_blocks(int n_agents, bool obs_f64);
 hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
                                  bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
                                  int nsteps, unsigned long long astride, int traj, int reload, uint32_t* mt,
-                                 const PoseDraw& D, const FinalOut& F, const PolicyArgs* policy = nullptr);
+                                 const PoseDraw& D, const FinalOut& F, const PolicyArgs* policy = nullptr,
+                                 const ValueArgs* critic = nullptr);
 hipError_t launch_tdm_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                      const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
                                      uint8_t* done, hipStream_t s, int nsteps, unsigned long long astride, int traj,
@@ -117,6 +118,7 @@ struct macm_world {
   FinalOut fin{};             // macm_world_set_final_outputs: the caller's buffers, kept until replaced or cleared
   // macm_world_set_policy: the caller's params buffer, kept until replaced or cleared (params NULL: none)
   macm_policy_mlp policy{0, 0, 0, 0, nullptr};
+  macm_value_mlp critic{0, 0, 0, 0, nullptr};  // macm_world_set_critic: likewise
   uint32_t* hstat = nullptr;  // host-mapped status word (B.host_status is its device alias)
   unsigned long long* bad = nullptr;  // validate_actions: first failing row (device scratch)
   // workgroup-path rollouts: env slices on streams of their own (created on first use)
@@ -943,9 +945,11 @@ static int rollout_wg_slices(macm_world* w, int S, const unsigned char* actions,
 
 // macm_world_rollout / _traj (bots = false) and macm_world_rollout_bots / _traj (bots = true);
 // macm_world_rollout_policy / _traj: the closed loop of bots = true with the registered policy as the
-// actor (pol: its params and this call's noise and logits; NULL: the scripted bot)
+// actor (pol: its params and this call's noise and logits; NULL: the scripted bot);
+// macm_world_rollout_policy_value / _traj: that with the registered critic beside the actor (crit: its
+// params and this call's values and boot; NULL: none)
 static int world_rollout(macm_world* w, const void* actions, int n_steps, const macm_outputs* out, void* stream,
-                         bool bots, bool traj, const PolicyArgs* pol = nullptr) {
+                         bool bots, bool traj, const PolicyArgs* pol = nullptr, const ValueArgs* crit = nullptr) {
   if (n_steps < 0) return fail(MACM_E_INVALID, "n_steps must be >= 0");
   if (n_steps == 0) return MACM_OK;  // nothing is read, so actions may be NULL (an empty tensor)
   if (!w || !actions || !out || !out->reward) return fail(MACM_E_INVALID, "world/actions/out/reward is NULL");
@@ -971,10 +975,11 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
     if (w->autoreset)  // the kernels with the in-launch reset
       HIP_TRY(launch_rollout_ar_w64(w->P, w->B, w->cur, actions, out->obs, w->cfg.obs_f64 != 0, out->nbr_id,
                                     out->reward, out->collided, out->done, s, n_steps, astride, traj ? 1 : 0,
-                                    w->roll_reload, w->mt, world_pose_draw(w), w->fin, pol));
+                                    w->roll_reload, w->mt, world_pose_draw(w), w->fin, pol, crit));
     else
       HIP_TRY(launch_rollout_w64(w->P, w->B, w->cur, actions, out->obs, w->cfg.obs_f64 != 0, out->nbr_id, out->reward,
-                                 out->collided, out->done, s, n_steps, astride, traj ? 1 : 0, w->roll_reload, pol));
+                                 out->collided, out->done, s, n_steps, astride, traj ? 1 : 0, w->roll_reload, pol,
+                                 crit));
     if (n_steps & 1) w->cur ^= 1;
     return MACM_OK;
   }
@@ -995,9 +1000,20 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
                              ok.collided, ok.done, s, handoff_for(w),
                              bots && !pol ? const_cast<unsigned char*>(act_k) + (traj ? rows * 3 : 0) : nullptr));
     w->cur ^= 1;
+    // the critic: the bootstrap value from the obs the step produced, before any reset; the value of the
+    // row the next action is taken from after it (without autoreset the same number: a device copy)
+    float* const boot_k = crit && crit->boot ? crit->boot + (traj ? (size_t)k * rows : 0) : nullptr;
+    float* const val_k = crit && crit->values ? crit->values + (traj ? (size_t)(k + 1) * rows : 0) : nullptr;
+    if (crit) {
+      float* const first = w->autoreset || boot_k ? boot_k : val_k;
+      if (first) HIP_TRY(launch_value_flock(*crit, ok.obs, w->cfg.obs_f64 != 0, obs_dim(w->cfg), rows, first, s));
+      if (!w->autoreset && boot_k && val_k)
+        HIP_TRY(hipMemcpyAsync(val_k, boot_k, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
     if (w->autoreset) {
       const int rc = world_autoreset_step(w, &ok, s);
       if (rc) return rc;
+      if (val_k) HIP_TRY(launch_value_flock(*crit, ok.obs, w->cfg.obs_f64 != 0, obs_dim(w->cfg), rows, val_k, s));
     }
     // autoreset: kernel C's fused bot acted on the terminal observation; the bots launch over every
     // row takes a reset env's next actions from its new initial obs (the other rows: the same actions)
@@ -1089,6 +1105,78 @@ int macm_world_rollout_policy(macm_world* w, uint8_t* actions, int32_t n_steps, 
 int macm_world_rollout_policy_traj(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise, float* logits,
                                    const macm_outputs* traj, void* stream) {
   return world_rollout_policy(w, actions, n_steps, noise, logits, traj, stream, true);
+}
+
+// A critic struct as the kernels can take it, as policy_check
+static int critic_check(const macm_value_mlp* c) {
+  if (c->in_dim != 4 && c->in_dim != 6) return fail(MACM_E_INVALID, "critic: in_dim must be 4 (polar) or 6 (cartesian)");
+  if (c->hidden != 16 && c->hidden != 32) return fail(MACM_E_INVALID, "critic: hidden must be 16 or 32");
+  if (c->n_hidden != 1 && c->n_hidden != 2) return fail(MACM_E_INVALID, "critic: n_hidden must be 1 or 2");
+  if (c->reserved != 0) return fail(MACM_E_INVALID, "critic: reserved must be 0");
+  if (!c->params) return fail(MACM_E_INVALID, "critic: params is NULL");
+  if (reinterpret_cast<uintptr_t>(c->params) & 15) return fail(MACM_E_INVALID, "critic: params must be 16-byte aligned");
+  return MACM_OK;
+}
+
+int macm_value_flock(const macm_value_mlp* c, const void* obs, int32_t obs_f64, int64_t rows, float* values,
+                     void* stream) {
+  if (!c) return fail(MACM_E_INVALID, "critic is NULL");
+  if (const int rc = critic_check(c)) return rc;
+  if (!obs || !values) return fail(MACM_E_INVALID, "obs/values is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "rows must be >= 0");
+  const ValueArgs V{c->params, nullptr, nullptr, c->hidden, c->n_hidden};
+  HIP_TRY(launch_value_flock(V, obs, obs_f64 != 0, c->in_dim, rows, values, (hipStream_t)stream));
+  return MACM_OK;
+}
+
+int macm_world_set_critic(macm_world* w, const macm_value_mlp* c) {
+  if (!w) return fail(MACM_E_INVALID, "world is NULL");
+  if (!c) {
+    w->critic = macm_value_mlp{0, 0, 0, 0, nullptr};
+    return MACM_OK;
+  }
+  if (const int rc = critic_check(c)) return rc;
+  if (w->cfg.action_mode != MACM_ACTION_DISCRETE)
+    return fail(MACM_E_UNSUPPORTED, "critic: it runs beside the MLP policy, which acts in discrete mode");
+  if (c->in_dim != obs_dim(w->cfg))
+    return fail(MACM_E_INVALID, "critic: in_dim " + std::to_string(c->in_dim) + " is not the world's obs_dim " +
+                                    std::to_string(obs_dim(w->cfg)));
+  w->critic = *c;
+  return MACM_OK;
+}
+
+static int world_rollout_policy_value(macm_world* w, uint8_t* actions, int n_steps, const float* noise, float* logits,
+                                      float* values, float* boot, const macm_outputs* out, void* stream, bool traj) {
+  if (n_steps < 0) return fail(MACM_E_INVALID, "n_steps must be >= 0");
+  if (n_steps == 0) return MACM_OK;
+  if (!w) return fail(MACM_E_INVALID, "world is NULL");
+  if (!values && !boot)
+    return fail(MACM_E_INVALID, "values and boot are both NULL (macm_world_rollout_policy serves that case)");
+  if (!w->policy.params) return fail(MACM_E_INVALID, "no policy is registered (macm_world_set_policy)");
+  if (!w->critic.params) return fail(MACM_E_INVALID, "no critic is registered (macm_world_set_critic)");
+  const PolicyArgs M{w->policy.params, noise, logits, w->policy.hidden, w->policy.n_hidden};
+  const ValueArgs V{w->critic.params, values, boot, w->critic.hidden, w->critic.n_hidden};
+  return world_rollout(w, actions, n_steps, out, stream, true, traj, &M, &V);
+}
+
+int macm_world_rollout_policy_value(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise, float* logits,
+                                    float* values, float* boot, const macm_outputs* out, void* stream) {
+  return world_rollout_policy_value(w, actions, n_steps, noise, logits, values, boot, out, stream, false);
+}
+
+int macm_world_rollout_policy_value_traj(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise,
+                                         float* logits, float* values, float* boot, const macm_outputs* traj,
+                                         void* stream) {
+  return world_rollout_policy_value(w, actions, n_steps, noise, logits, values, boot, traj, stream, true);
+}
+
+int macm_gae(const float* reward, const float* values, const float* boot, const uint8_t* done, int32_t n_steps,
+             int32_t n_envs, int32_t n_agents, float gamma, float lambda, float* adv, float* ret, void* stream) {
+  if (!reward || !values || !boot || !done || !adv || !ret)
+    return fail(MACM_E_INVALID, "gae: reward/values/boot/done/adv/ret is NULL");
+  if (n_steps < 0 || n_envs < 0 || n_agents < 0) return fail(MACM_E_INVALID, "gae: n_steps, n_envs, n_agents must be >= 0");
+  HIP_TRY(launch_gae(reward, values, boot, done, n_steps, n_envs, n_agents, gamma, lambda, adv, ret, (hipStream_t)stream));
+  return MACM_OK;
 }
 
 int macm_world_observe(macm_world* w, const macm_outputs* out, void* stream) {

@@ -1,7 +1,7 @@
 // policy_mlp.hpp — one agent's decision of a learned policy: a float32 MLP over the agent's obs row,
 // shared by the one-shot kernel (policy.hip, macm_policy_flock) and the closed-loop rollouts
 // (flock_step_w64.hip / rollout_autoreset.inc, macm_world_rollout_policy), where it stands in the
-// place of the scripted bot (bots.hpp).
+// place of the scripted bot (bots.hpp); and the critic beside it (macm_value_mlp, below).
 //
 // The definition (include/macm.h, macm_policy_mlp), all float32:
 //   x[q]  = (float)obs[q], q < OD (a float64 obs rounds to nearest)
@@ -111,7 +111,55 @@ __device__ __forceinline__ void policy_mlp_row(const PolicyArgs& M, int od, cons
   }
 }
 
-// host side (C++ linkage, macm_capi.hip): the one-shot kernel over rows (policy.hip)
+// The critic (include/macm.h, macm_value_mlp): a second MLP of the same arithmetic over the same obs
+// row, with a trunk of its own and one output, V(obs). What the kernels take of a registered critic
+// and of one rollout call (device pointers):
+struct ValueArgs {
+  const float* params;  // W1[OD][H], b1[H], (W2[H][H], b2[H]), W3[H][1], b3[1]; 16-byte aligned
+  float* values;        // rollouts: [E, N], or [K + 1, E, N] with traj (row 0 is the caller's); NULL: not wanted
+  float* boot;          // rollouts: [E, N], or [K, E, N] with traj; NULL: not wanted
+  int32_t hidden;       // H: 16 or 32
+  int32_t n_hidden;     // 1 or 2
+};
+
+template <typename OT, int OD, int H>
+__device__ __forceinline__ float value_mlp_row_t(policy_cptr p, int n_hidden, const OT* __restrict__ o) {
+  float x[OD];
+#pragma unroll
+  for (int q = 0; q < OD; ++q) x[q] = (float)o[q];
+  float h[H];
+  policy_layer<OD, H, true>(p, p + OD * H, x, h);
+  p += OD * H + H;
+  if (n_hidden == 2) {  // wave-uniform
+    float g[H];
+    policy_layer<H, H, true>(p, p + H * H, h, g);
+#pragma unroll
+    for (int j = 0; j < H; ++j) h[j] = g[j];
+    p += H * H + H;
+  }
+  float y[1];
+  policy_layer<H, 1, false>(p, p + H, h, y);
+  return y[0];
+}
+
+// V of the agent's obs row o (od = 4 polar / 6 cartesian) as stored. V.params, V.hidden and V.n_hidden
+// must be wave-uniform.
+template <typename OT>
+__device__ __forceinline__ float value_mlp_row(const ValueArgs& V, int od, const OT* __restrict__ o) {
+  const policy_cptr p = (policy_cptr)(unsigned long long)V.params;
+  if (od == 6) {
+    if (V.hidden == 32) return value_mlp_row_t<OT, 6, 32>(p, V.n_hidden, o);
+    return value_mlp_row_t<OT, 6, 16>(p, V.n_hidden, o);
+  }
+  if (V.hidden == 32) return value_mlp_row_t<OT, 4, 32>(p, V.n_hidden, o);
+  return value_mlp_row_t<OT, 4, 16>(p, V.n_hidden, o);
+}
+
+// host side (C++ linkage, macm_capi.hip): the one-shot kernels over rows and the GAE kernel (policy.hip)
+hipError_t launch_value_flock(const ValueArgs& V, const void* obs, bool obs_f64, int od, long long rows, float* values,
+                              hipStream_t s);
+hipError_t launch_gae(const float* reward, const float* values, const float* boot, const uint8_t* done, int n_steps,
+                      long long n_envs, int n_agents, float gamma, float lambda, float* adv, float* ret, hipStream_t s);
 hipError_t launch_policy_flock(const PolicyArgs& M, const void* obs, bool obs_f64, int od, long long rows,
                                uint8_t* act, hipStream_t s);
 

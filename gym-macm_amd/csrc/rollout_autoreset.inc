@@ -201,6 +201,12 @@ struct RolloutArArgs<ObsPol<OT>> : RolloutArArgs<OT> {
   PolicyArgs pol;  // noise [K, E, N, 9], logits [E, N, 9] or [K, E, N, 9] with A.traj
 };
 
+// a registered critic beside the policy (ObsPolV): its fields follow the policy's
+template <typename OT>
+struct RolloutArArgs<ObsPolV<OT>> : RolloutArArgs<ObsPol<OT>> {
+  ValueArgs val;  // values [E, N] or [K + 1, E, N], boot [E, N] or [K, E, N] with A.traj
+};
+
 // env_rollout_w64 with the in-launch reset; no tail or split observation (their pose snapshots know
 // nothing of a mid-launch respawn: TDM observes inside the step).
 // OTA: OT or ObsEv<OT>, as env_rollout_w64. The step writes the events, the in-launch reset none: it
@@ -210,6 +216,7 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
   using OT = typename ObsTag<OTA>::type;
   constexpr bool EV = ObsTag<OTA>::ev;
   constexpr bool POL = ObsTag<OTA>::pol;
+  constexpr bool VAL = ObsTag<OTA>::val;
   static_assert(!EV || MODE == kTdm, "combat events are TDM's");
   static_assert(!POL || (MODE == kFlock && !CARRY), "the MLP policy acts in Flock's closed loop");
   const int nsteps = R0.A.nsteps;
@@ -244,8 +251,13 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
     const size_t abytes = MODE == kTdm ? 4 : 3;  // closed loop: uint8 actions per agent
     uint8_t* const pol_in = A.policy_act ? A.policy_act + kr * EN * abytes : nullptr;
     __builtin_amdgcn_s_setprio(0);  // as at a launch: the chain raises it again
+    // (with the critic as well: the step's lane-derived addresses held across all K steps beside the
+    // critic's registers cost the N = 64 kernels a VGPR in scratch. Masked back to its range there:
+    // the helpers the Flock kernels share are specialised on the range of the lane they are called with,
+    // and an unbounded one here changed the code of every other Flock kernel of the unit.)
     int sl = (int)threadIdx.x;
-    if constexpr (MODE == kTdm) asm volatile("" : "+v"(sl));
+    if constexpr (MODE == kTdm || VAL) asm volatile("" : "+v"(sl));
+    if constexpr (VAL) sl &= W - 1;
     void* lds = nullptr;  // the step's contact pool, dead once the step ends
     const int near_ctl = (kNearL ? near_keep | ((A.cur & kRollNearPlainBit) ? kNearCtlPlain : 0) : 0) |
                          (CARRY && (A.cur & kRollReloadBit) ? kStepCtlWriteBack : 0);
@@ -267,7 +279,8 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
     // (TDM: the lane index opaque once more, or what the reset derives from it is computed before
     // the step and held across it: 5 VGPRs in scratch)
     int rl = (int)threadIdx.x;
-    if constexpr (MODE == kTdm) asm volatile("" : "+v"(rl));
+    if constexpr (MODE == kTdm || VAL) asm volatile("" : "+v"(rl));
+    if constexpr (VAL) rl &= W - 1;
     int dn = 0;
     if (rl == 0) dn = A.B.done[env];
     dn = __builtin_amdgcn_readfirstlane(dn);
@@ -279,7 +292,31 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     }
     __syncthreads();
-    if (dn) {
+    if constexpr (VAL) {
+      // The critic around the reset, one copy of its code: pass 0 on the obs row the step stored (the
+      // bootstrap value, before final_copy_w64 / reset_env_w64 take the row); an env that ended resets and
+      // takes a second pass on its new initial obs, behind the reset's fence. The value of the row the
+      // next action is taken from is the last pass's (an env that did not end: the bootstrap value).
+      int passes = dn ? 2 : 1;  // wave-uniform
+      asm volatile("" : "+s"(passes));
+#pragma nounroll
+      for (int ps = 0; ps < passes; ++ps) {
+        if (ps) {
+          final_copy_w64<MODE, OT>(R.F, A.B, N, (int)od, obs, nbr, TB.mask_out, env, rl);
+          reset_env_w64<MODE, OT>(A.P, A.B, A.TP, TB, R.D, R.mt, (A.cur ^ (k + 1)) & 1, obs, nbr, env, rl, lds);
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+          __syncthreads();
+        }
+        // (the lane index opaque: else the row's addresses are computed before the step and held across it)
+        int vl = (int)threadIdx.x;
+        asm volatile("" : "+v"(vl));
+        if (vl < N) {
+          const size_t row = (size_t)env * N + vl;
+          value_store_row(R.val, value_mlp_row<OT>(R.val, (int)od, obs + row * od), row, (size_t)k, kr, EN, A.traj != 0,
+                          ps == 0);
+        }
+      }
+    } else if (dn) {
       // behind the fence: the reset's stores follow the step's to the same rows (state, list, obs);
       // before them, the rows they overwrite go to the registered final outputs
       final_copy_w64<MODE, OT>(R.F, A.B, N, (int)od, obs, nbr, TB.mask_out, env, rl);
@@ -313,7 +350,7 @@ static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hip
                            const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur, const void* actions,
                            void* obs, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, int reload, uint32_t* mt,
                            const PoseDraw& D, const FinalOut& F, int32_t* hit_out = nullptr,
-                           const PolicyArgs* policy = nullptr) {
+                           const PolicyArgs* policy = nullptr, const ValueArgs* critic = nullptr) {
   // astride == 0: closed loop, `actions` is the bots' action buffer
   uint8_t* pol = astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(actions)) : nullptr;
   if (B.sched && nsteps >= kRollBalanceMinSteps) {  // the balanced env order, as launch_roll
@@ -334,6 +371,14 @@ static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hip
       return;
     }
     if (NCAP == 64 && (reload & 2)) R.A.cur |= kRollNearPlainBit;
+    if (policy && critic) {  // and a registered critic: the kernel that evaluates it beside the actor
+      RolloutArArgs<ObsPolV<OT>> V;
+      static_cast<RolloutArArgs<OT>&>(V) = R;
+      V.pol = *policy;
+      V.val = *critic;
+      hipLaunchKernelGGL((env_rollout_ar_w64<kFlock, NCAP, ObsPolV<OT>, SCAL>), dim3(P.n_envs), dim3(W), 0, s, V);
+      return;
+    }
     if (policy) {  // a registered policy: the kernel with the MLP where the bot is
       RolloutArArgs<ObsPol<OT>> V;
       static_cast<RolloutArArgs<OT>&>(V) = R;
@@ -355,27 +400,28 @@ static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hip
 hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
                                  bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
                                  int nsteps, unsigned long long astride, int traj, int reload, uint32_t* mt,
-                                 const PoseDraw& D, const FinalOut& F, const PolicyArgs* policy) {
+                                 const PoseDraw& D, const FinalOut& F, const PolicyArgs* policy,
+                                 const ValueArgs* critic) {
   const TdmParams TP{};
   const TdmBuffers TB{};
   const bool small = P.n_agents <= 32;
   if (obs_f64) {
     if (small)
       launch_roll_ar<kFlock, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                        reload, mt, D, F, nullptr, policy);
+                                        reload, mt, D, F, nullptr, policy, critic);
     else
       launch_roll_ar<kFlock, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                        reload, mt, D, F, nullptr, policy);
+                                        reload, mt, D, F, nullptr, policy, critic);
   } else {
     if (small)
       launch_roll_ar<kFlock, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                       reload, mt, D, F, nullptr, policy);
+                                       reload, mt, D, F, nullptr, policy, critic);
     else if (P.n_envs >= kScalarSweepMinEnvs)
       launch_roll_ar<kFlock, 64, float, true>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll,
-                                             done, reload, mt, D, F, nullptr, policy);
+                                             done, reload, mt, D, F, nullptr, policy, critic);
     else
       launch_roll_ar<kFlock, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                       reload, mt, D, F, nullptr, policy);
+                                       reload, mt, D, F, nullptr, policy, critic);
   }
   return hipGetLastError();
 }

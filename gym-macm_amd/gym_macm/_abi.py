@@ -89,6 +89,13 @@ class MacmPolicyMlp(Structure):
                 ("params", c_void_p)]
 
 
+class MacmValueMlp(Structure):
+    """macm_value_mlp: a float32 MLP critic over Flock obs rows; params is a device pointer to
+    W1[in][hidden], b1, (W2[hidden][hidden], b2), W3[hidden][1], b3, 16-byte aligned."""
+    _fields_ = [("in_dim", c_int32), ("hidden", c_int32), ("n_hidden", c_int32), ("reserved", c_int32),
+                ("params", c_void_p)]
+
+
 class MacmState(Structure):
     _fields_ = [(n, c_void_p) for n in (
         "pos", "vel", "angle", "fat", "sleep", "targets", "contact_count", "contact_ab",
@@ -264,6 +271,14 @@ SIGNATURES = {
                                           c_void_p]),
     "macm_world_rollout_policy_traj": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, POINTER(MacmOutputs),
                                                c_void_p]),
+    "macm_value_flock": (c_int, [POINTER(MacmValueMlp), c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
+    "macm_world_set_critic": (c_int, [c_void_p, POINTER(MacmValueMlp)]),
+    "macm_world_rollout_policy_value": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                POINTER(MacmOutputs), c_void_p]),
+    "macm_world_rollout_policy_value_traj": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                                     c_void_p, POINTER(MacmOutputs), c_void_p]),
+    "macm_gae": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float,
+                         c_void_p, c_void_p, c_void_p]),
     "macm_bots_flock": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
     "macm_bots_combat": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
 }

@@ -14,6 +14,15 @@ recomputes log-probabilities from the stored logits; the device draws nothing.
 ``params`` is one flat device tensor, W[in][out] row-major then the bias, layer after layer. The
 library reads it at every launch, so a learner that writes new values into it in place
 (``pack`` / ``load_linear_layers`` / ``params.copy_``) needs no second registration.
+
+The critic beside the actor (macm_value_mlp) is a second MLP of the same arithmetic with one output,
+and ``gae`` turns a trajectory into advantages and returns in one launch:
+
+    crit = MlpCritic.from_linear_layers([v.fc1, v.fc2, v.head], device="cuda:0"); vec.set_critic(crit)
+    vals = torch.empty((K + 1, E, N), device=dev); vals[0] = crit.value(vec.obs)
+    boot = torch.empty((K, E, N), device=dev)
+    traj = vec.rollout_policy(acts, K, noise=g, trajectory=True, logits=lg, values=vals, boot=boot)
+    adv, ret = gae(traj["reward"], vals[:K], boot, traj["done"], 0.99, 0.95)
 """
 from __future__ import annotations
 
@@ -26,43 +35,44 @@ from . import _abi
 N_LOGITS = 9
 
 
-def layer_shapes(in_dim: int, hidden: int, n_hidden: int) -> list:
-    """[(in, out)] of the layers: n_hidden hidden layers, then the 9 logits."""
-    dims = [int(in_dim)] + [int(hidden)] * int(n_hidden) + [N_LOGITS]
+def layer_shapes(in_dim: int, hidden: int, n_hidden: int, n_out: int = N_LOGITS) -> list:
+    """[(in, out)] of the layers: n_hidden hidden layers, then the n_out outputs (the 9 logits; a critic: 1)."""
+    dims = [int(in_dim)] + [int(hidden)] * int(n_hidden) + [int(n_out)]
     return list(zip(dims[:-1], dims[1:]))
 
 
-def n_params(in_dim: int, hidden: int, n_hidden: int) -> int:
-    return sum(i * o + o for i, o in layer_shapes(in_dim, hidden, n_hidden))
+def n_params(in_dim: int, hidden: int, n_hidden: int, n_out: int = N_LOGITS) -> int:
+    return sum(i * o + o for i, o in layer_shapes(in_dim, hidden, n_hidden, n_out))
 
 
 def _stream(t):
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-class MlpPolicy:
-    """in_dim: the world's obs_dim (4 polar, 6 cartesian); hidden 16 or 32; n_hidden 1 or 2."""
+class _Mlp:
+    """What MlpPolicy and MlpCritic share: the flat params tensor, its layout and the C-ABI struct."""
+    N_OUT, STRUCT, WHAT = None, None, None  # the subclass's outputs, _abi struct and name in messages
 
     def __init__(self, in_dim: int, hidden: int, n_hidden: int, device=None):
         if int(in_dim) not in (4, 6) or int(hidden) not in (16, 32) or int(n_hidden) not in (1, 2):
-            raise ValueError("MlpPolicy: in_dim must be 4 or 6, hidden 16 or 32, n_hidden 1 or 2")
+            raise ValueError(f"{type(self).__name__}: in_dim must be 4 or 6, hidden 16 or 32, n_hidden 1 or 2")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise ValueError("the policy's params live on a GPU device (no CPU fallback)")
+            raise ValueError(f"the {self.WHAT}'s params live on a GPU device (no CPU fallback)")
         self.in_dim, self.hidden, self.n_hidden = int(in_dim), int(hidden), int(n_hidden)
-        self.shapes = layer_shapes(in_dim, hidden, n_hidden)
-        self.params = torch.zeros((n_params(in_dim, hidden, n_hidden),), dtype=torch.float32, device=self.device)
+        self.shapes = layer_shapes(in_dim, hidden, n_hidden, self.N_OUT)
+        self.params = torch.zeros((n_params(in_dim, hidden, n_hidden, self.N_OUT),), dtype=torch.float32,
+                                  device=self.device)
         assert self.params.data_ptr() % 16 == 0
-        self._struct = _abi.MacmPolicyMlp(self.in_dim, self.hidden, self.n_hidden, 0,
-                                          ctypes.c_void_p(self.params.data_ptr()))
+        self._struct = self.STRUCT(self.in_dim, self.hidden, self.n_hidden, 0, ctypes.c_void_p(self.params.data_ptr()))
 
-    def struct(self) -> "_abi.MacmPolicyMlp":
+    def struct(self):
         """The C-ABI struct (it points into ``params``: this object must outlive its uses)."""
         return self._struct
 
-    def pack(self, weights, biases) -> "MlpPolicy":
+    def pack(self, weights, biases):
         """weights[l]: [in, out] (already transposed), biases[l]: [out]; written into params in place."""
         if len(weights) != len(self.shapes) or len(biases) != len(self.shapes):
             raise ValueError(f"expected {len(self.shapes)} layers")
@@ -86,19 +96,25 @@ class MlpPolicy:
             at += o
         return ws, bs
 
-    def load_linear_layers(self, layers) -> "MlpPolicy":
+    def load_linear_layers(self, layers):
         """The weights of torch.nn.Linear layers ([out, in] each), transposed to [in][out], into params."""
         return self.pack([l.weight.detach().t().contiguous() for l in layers], [l.bias.detach() for l in layers])
 
     @classmethod
-    def from_linear_layers(cls, layers, device=None) -> "MlpPolicy":
-        """layers: the hidden torch.nn.Linear layers (relu between them) and the 9-logit head."""
+    def from_linear_layers(cls, layers, device=None):
+        """layers: the hidden torch.nn.Linear layers (relu between them) and the head (9 logits; a critic: 1)."""
         layers = list(layers)
-        if len(layers) not in (2, 3) or layers[-1].out_features != N_LOGITS:
-            raise ValueError("expected 1 or 2 hidden nn.Linear layers and a head with 9 outputs")
+        if len(layers) not in (2, 3) or layers[-1].out_features != cls.N_OUT:
+            raise ValueError(f"expected 1 or 2 hidden nn.Linear layers and a head with {cls.N_OUT} output"
+                             + ("s" if cls.N_OUT != 1 else ""))
         if device is None:
             device = layers[0].weight.device
         return cls(layers[0].in_features, layers[0].out_features, len(layers) - 1, device).load_linear_layers(layers)
+
+
+class MlpPolicy(_Mlp):
+    """in_dim: the world's obs_dim (4 polar, 6 cartesian); hidden 16 or 32; n_hidden 1 or 2."""
+    N_OUT, STRUCT, WHAT = N_LOGITS, _abi.MacmPolicyMlp, "policy"
 
     def act(self, obs: torch.Tensor, noise: torch.Tensor = None, logits: torch.Tensor = None,
             out: torch.Tensor = None) -> torch.Tensor:
@@ -125,3 +141,64 @@ class MlpPolicy:
                                            obs.numel() // self.in_dim, p(noise), p(out), p(logits), _stream(obs)),
                        "macm_policy_flock")
         return out
+
+
+class MlpCritic(_Mlp):
+    """The critic beside the actor (macm_value_mlp): the same MLP with a trunk of its own and one output,
+    V(obs). Its shape (hidden 16 or 32, n_hidden 1 or 2) is independent of the actor's."""
+    N_OUT, STRUCT, WHAT = 1, _abi.MacmValueMlp, "critic"
+
+    def value(self, obs: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+        """V (float32 [...]) of obs [..., in_dim] (macm_value_flock)."""
+        if obs.device != self.device or not obs.is_contiguous() or obs.dtype not in (torch.float32, torch.float64):
+            raise ValueError("obs must be a contiguous float32/float64 tensor on the critic's device")
+        if obs.shape[-1] != self.in_dim:
+            raise ValueError(f"obs rows must have {self.in_dim} values")
+        lead = tuple(obs.shape[:-1])
+        if out is None:
+            out = torch.empty(lead, dtype=torch.float32, device=self.device)
+        elif (out.device != self.device or not out.is_contiguous() or out.dtype != torch.float32
+              or tuple(out.shape) != lead):
+            raise ValueError(f"out must be a contiguous float32 {lead} tensor on the critic's device")
+        with torch.cuda.device(self.device):
+            _abi.check(_abi.lib().macm_value_flock(ctypes.byref(self._struct), ctypes.c_void_p(obs.data_ptr()),
+                                                   1 if obs.dtype == torch.float64 else 0, obs.numel() // self.in_dim,
+                                                   ctypes.c_void_p(out.data_ptr()), _stream(obs)), "macm_value_flock")
+        return out
+
+
+def gae(reward: torch.Tensor, values: torch.Tensor, boot: torch.Tensor, done: torch.Tensor, gamma: float, lam: float,
+        adv: torch.Tensor = None, ret: torch.Tensor = None):
+    """(adv, ret), float32 [K, E, N]: generalised advantage estimation over a trajectory in one launch
+    (macm_gae). reward, values and boot are float32 [K, E, N] (values: the first K rows of the launch's
+    [K + 1, E, N] buffer), done uint8 [K, E]; boot[k] is V of the observation step k produced, so every
+    end bootstraps from its own terminal observation, and a done row cuts the recursion."""
+    dev = reward.device
+    if reward.dim() != 3:
+        raise ValueError("reward must be a [K, E, N] tensor")
+    K, E, N = (int(d) for d in reward.shape)
+    if adv is None:
+        adv = torch.empty((K, E, N), dtype=torch.float32, device=dev)
+    if ret is None:
+        ret = torch.empty((K, E, N), dtype=torch.float32, device=dev)
+    for name, t in (("reward", reward), ("values", values), ("boot", boot), ("adv", adv), ("ret", ret)):
+        if (t.device != dev or not t.is_contiguous() or t.dtype != torch.float32 or tuple(t.shape) != (K, E, N)):
+            raise ValueError(f"{name} must be a contiguous float32 {[K, E, N]} tensor on {dev}")
+    if done.device != dev or not done.is_contiguous() or done.dtype != torch.uint8 or tuple(done.shape) != (K, E):
+        raise ValueError(f"done must be a contiguous uint8 {[K, E]} tensor on {dev}")
+    ins = (reward, values, boot, done)
+    for name, o in (("adv", adv), ("ret", ret)):
+        if any(_overlap(o, i) for i in ins) or (name == "ret" and _overlap(o, adv)):
+            raise ValueError(f"{name} must not alias an input or the other output")
+    if dev.type != "cuda":
+        raise ValueError("gae runs on a GPU device (no CPU fallback)")
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        _abi.check(_abi.lib().macm_gae(p(reward), p(values), p(boot), p(done), K, E, N, float(gamma), float(lam),
+                                       p(adv), p(ret), _stream(reward)), "macm_gae")
+    return adv, ret
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a.numel() > 0 and b.numel() > 0 and a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()

@@ -126,12 +126,21 @@ class FlockVec(object):
         """Register the actor of rollout_policy: a gym_macm.policy.MlpPolicy, or None (World.set_policy)."""
         self.world.set_policy(policy)
 
-    def rollout_policy(self, actions, n_steps, noise=None, trajectory=False, traj=None, logits=None):
+    def set_critic(self, critic) -> None:
+        """Register the critic of rollout_policy(..., values=, boot=): a gym_macm.policy.MlpCritic, or None
+        (World.set_critic)."""
+        self.world.set_critic(critic)
+
+    def rollout_policy(self, actions, n_steps, noise=None, trajectory=False, traj=None, logits=None, values=None,
+                       boot=None):
         """n_steps of the closed loop step -> policy -> step in one launch, beside rollout_bots: the
         registered MlpPolicy acts on the observation each step wrote (World.rollout_policy). ``noise``
         [n_steps, E, N, 9] samples (None: argmax); ``logits`` keeps what the policy computed. With
-        ``autoreset`` an env that ends restarts inside the launch and acts on its new initial obs."""
-        return self.world.rollout_policy(actions, n_steps, noise=noise, trajectory=trajectory, traj=traj, logits=logits)
+        ``autoreset`` an env that ends restarts inside the launch and acts on its new initial obs.
+        ``values`` / ``boot``: the registered critic's V of every row and the bootstrap value of every
+        step, from the same launch."""
+        return self.world.rollout_policy(actions, n_steps, noise=noise, trajectory=trajectory, traj=traj, logits=logits,
+                                         values=values, boot=boot)
 
     def reset_envs(self, mask=None):
         """New episodes in the masked envs (see World.reset_envs)."""

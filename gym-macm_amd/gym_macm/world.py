@@ -112,6 +112,7 @@ class World:
         self._out_obs = _abi.MacmOutputs(_ptr(self.obs), _ptr(self.nbr_id), None, None, None)
         self.final_obs = self.final_nbr_id = self.final_length = self.final_ends = None  # set_final_outputs
         self.policy = None  # set_policy
+        self.critic = None  # set_critic
 
     def __del__(self):
         h = getattr(self, "h", None)
@@ -348,8 +349,22 @@ class World:
         _abi.check(self.L.macm_world_set_policy(self.h, ctypes.byref(policy.struct())), "macm_world_set_policy")
         self.policy = policy
 
+    def set_critic(self, critic) -> None:
+        """Register the critic of rollout_policy(..., values=, boot=) (macm_world_set_critic): a
+        gym_macm.policy.MlpCritic, or None to clear. As set_policy: ``critic.params`` is read at every
+        launch, and this object keeps the critic alive."""
+        if critic is None:
+            _abi.check(self.L.macm_world_set_critic(self.h, None), "macm_world_set_critic")
+            self.critic = None
+            return
+        if critic.device != self.device:
+            raise ValueError(f"the critic's params must be on {self.device}")
+        _abi.check(self.L.macm_world_set_critic(self.h, ctypes.byref(critic.struct())), "macm_world_set_critic")
+        self.critic = critic
+
     def rollout_policy(self, actions: torch.Tensor, n_steps: int, noise: torch.Tensor = None, trajectory: bool = False,
-                       traj: dict = None, logits: torch.Tensor = None):
+                       traj: dict = None, logits: torch.Tensor = None, values: torch.Tensor = None,
+                       boot: torch.Tensor = None):
         """n_steps of the closed loop step -> policy -> step with the registered policy as the actor,
         one launch on the wave path (macm_world_rollout_policy / _traj), as rollout_bots is for the bot.
         actions: uint8 [E, N, 3], the first step's on entry (``policy.act(self.obs)``) and the next on
@@ -357,6 +372,12 @@ class World:
         noise: float32 [n_steps, E, N, 9] or None (argmax); row k decides after step k.
         logits: float32 [E, N, 9] (the last step's remain), with ``trajectory`` [n_steps, E, N, 9], or
         None; row k holds the logits computed from obs row k.
+        values / boot: with either given, the registered critic runs beside the actor
+        (macm_world_rollout_policy_value / _traj). boot, float32 [E, N] or with ``trajectory``
+        [n_steps, E, N]: row k is V of the observation step k produced, before any reset (the bootstrap
+        value of every end inside the launch). values, float32 [E, N] or with ``trajectory``
+        [n_steps + 1, E, N]: row k + 1 is V of obs row k as it stands after the step and any reset; row
+        0 is the caller's (``critic.value(self.obs)``) and is left alone.
         Returns (obs, nbr_id, reward, done), or with ``trajectory`` the dict of rollout_traj()."""
         K, E, N = int(n_steps), self.E, self.N
         ashape = (K + 1, E, N, 3) if trajectory else (E, N, 3)
@@ -367,6 +388,25 @@ class World:
             if t is not None and (t.device != self.device or not t.is_contiguous() or t.dtype != torch.float32
                                   or tuple(t.shape) != shp):
                 raise ValueError(f"{name} must be a contiguous float32 {list(shp)} tensor on the world's device")
+        for name, t, shp in (("values", values, (K + 1, E, N) if trajectory else (E, N)),
+                             ("boot", boot, (K, E, N) if trajectory else (E, N))):
+            if t is not None and (t.device != self.device or not t.is_contiguous() or t.dtype != torch.float32
+                                  or tuple(t.shape) != shp):
+                raise ValueError(f"{name} must be a contiguous float32 {list(shp)} tensor on the world's device")
+        if values is not None or boot is not None:  # the critic beside the actor
+            if not trajectory:
+                _abi.check(self.L.macm_world_rollout_policy_value(self.h, _ptr(actions), K, _ptr(noise), _ptr(logits),
+                                                                  _ptr(values), _ptr(boot), ctypes.byref(self._out),
+                                                                  self._stream()), "macm_world_rollout_policy_value")
+                return self.obs, self.nbr_id, self.reward, self.done
+            traj = self.trajectory_buffers(K) if traj is None else traj
+            out = self._traj_out(traj, K)
+            _abi.check(self.L.macm_world_rollout_policy_value_traj(self.h, _ptr(actions), K, _ptr(noise), _ptr(logits),
+                                                                   _ptr(values), _ptr(boot), ctypes.byref(out),
+                                                                   self._stream()), "macm_world_rollout_policy_value_traj")
+            if K > 0:
+                self._keep_last(traj, K)
+            return traj
         if not trajectory:
             _abi.check(self.L.macm_world_rollout_policy(self.h, _ptr(actions), K, _ptr(noise), _ptr(logits),
                                                         ctypes.byref(self._out), self._stream()),
@@ -387,6 +427,14 @@ class World:
         self.L.macm_world_rollout_policy(self.h, ctypes.c_void_p(actions_ptr), int(n_steps),
                                          ctypes.c_void_p(noise_ptr or None), ctypes.c_void_p(logits_ptr or None),
                                          ctypes.byref(self._out), ctypes.c_void_p(stream_handle))
+
+    def rollout_policy_value_raw(self, actions_ptr: int, n_steps: int, noise_ptr: int, logits_ptr: int,
+                                 values_ptr: int, boot_ptr: int, stream_handle: int) -> None:
+        """rollout_policy_raw with the registered critic beside the actor; 0 = not wanted (not both)."""
+        self.L.macm_world_rollout_policy_value(self.h, ctypes.c_void_p(actions_ptr), int(n_steps),
+                                               ctypes.c_void_p(noise_ptr or None), ctypes.c_void_p(logits_ptr or None),
+                                               ctypes.c_void_p(values_ptr or None), ctypes.c_void_p(boot_ptr or None),
+                                               ctypes.byref(self._out), ctypes.c_void_p(stream_handle))
 
     def observe(self):
         _abi.check(self.L.macm_world_observe(self.h, ctypes.byref(self._out_obs), self._stream()),

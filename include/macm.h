@@ -532,6 +532,84 @@ int macm_world_rollout_policy(macm_world* w, uint8_t* actions, int32_t n_steps, 
 int macm_world_rollout_policy_traj(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise,
                                    float* logits, const macm_outputs* traj, void* stream);
 
+/*
+ * A critic beside the actor: a second float32 MLP over the same obs row, with a trunk of its own and
+ * one output, V(obs), so that a PPO / A2C collector gets the values of every row and the bootstrap
+ * value of every step from the launch that steps the envs. The arithmetic is macm_policy_mlp's, word
+ * for word: x[q] = (float)obs[q]; each layer the k-ordered fmaf chain from the bias, one rounding per
+ * step; relu(v) = v > 0 ? v : +0.0f on the hidden layers, none on the last. Denormals are kept; the
+ * sign and payload of a NaN are unspecified.
+ *   params: device float32, 16-byte aligned, row-major [in][out]:
+ *           W1[in_dim][hidden], b1[hidden], (W2[hidden][hidden], b2[hidden] if n_hidden == 2),
+ *           W3[hidden][1], b3[1].
+ * hidden is 16 or 32, n_hidden 1 or 2, in_dim 4 (polar) or 6 (cartesian), reserved 0; the critic's
+ * shape is independent of the actor's. Additive: MACM_ABI_VERSION stays 9.
+ */
+typedef struct macm_value_mlp {
+  int32_t in_dim, hidden, n_hidden, reserved;
+  const float* params;
+} macm_value_mlp;
+
+/*
+ * V of `rows` obs rows ([rows, in_dim], float32 or float64 as obs_f64) into values [rows]: the values
+ * of a rollout's first row, and what the per-step loop calls.
+ * MACM_E_INVALID: c NULL or outside the shapes above, params NULL or misaligned, obs or values NULL,
+ * rows < 0. rows = 0 writes nothing.
+ */
+int macm_value_flock(const macm_value_mlp* c, const void* obs, int32_t obs_f64, int64_t rows, float* values,
+                     void* stream);
+
+/*
+ * Registers the critic of macm_world_rollout_policy_value: a registration, as macm_world_set_policy
+ * (the world keeps the struct, not the params buffer; the learner may overwrite params between
+ * launches; c NULL clears). MACM_E_INVALID, nothing changed: a NULL world, a struct outside the shapes
+ * above, reserved != 0, params NULL or misaligned, in_dim other than the world's obs_dim.
+ * MACM_E_UNSUPPORTED: a continuous-action world. A world with a critic registered runs every other
+ * entry point exactly as without one.
+ */
+int macm_world_set_critic(macm_world* w, const macm_value_mlp* c);
+
+/*
+ * macm_world_rollout_policy / _traj, bit for bit, and in addition for step k of env e:
+ *   boot   row k receives V of the observation step k produced, before any reset. With autoreset on,
+ *          in a step that sets done, that is the row that goes to the final outputs' obs: every end
+ *          inside the launch has its bootstrap value, where the final outputs keep only an env's last
+ *          end. (4 B per agent-step; the terminal observation row itself is not kept per trajectory
+ *          row: it would double the largest buffer, and its main use is this number.)
+ *   values row k + 1 receives V of the observation the action of step k + 1 is taken from: obs row k as
+ *          it stands after the step and any reset (a reset env: its new initial obs). When the env
+ *          did not end, values[k + 1] and boot[k] hold the same bits.
+ * Trajectory form: values [n_steps + 1, E, N], row 0 is the caller's (macm_value_flock on the
+ * initial obs) and is neither read nor written; boot [n_steps, E, N]. Overwrite form: values [E, N],
+ * V of the obs the returned next actions come from; boot [E, N], the last step's bootstrap value.
+ * Either of values and boot may be NULL: not wanted, never stored to. Both NULL: MACM_E_INVALID (the
+ * plain entry point serves that case). MACM_E_INVALID, nothing changed or launched, without a
+ * registered critic or policy. n_steps = 0 does nothing. One launch on the wave path (N <= 64); on
+ * the other paths the launches of the per-step loop. Same results as n_steps of
+ *   macm_world_step, macm_value_flock (boot), [reset_envs(done)], macm_policy_flock, macm_value_flock (values).
+ */
+int macm_world_rollout_policy_value(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise,
+                                    float* logits, float* values, float* boot, const macm_outputs* out,
+                                    void* stream);
+int macm_world_rollout_policy_value_traj(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise,
+                                         float* logits, float* values, float* boot, const macm_outputs* traj,
+                                         void* stream);
+
+/*
+ * Generalised advantage estimation over a trajectory, any env kind, all float32. reward, values, boot,
+ * adv and ret are [n_steps, E, N] (values may point at the first n_steps rows of the launch's
+ * [n_steps + 1, E, N] buffer); done is [n_steps, E], any nonzero byte counts as done. With
+ * gl = gamma * lambda (one float32 multiply) and carry = +0.0f, for k from n_steps - 1 down to 0:
+ *   delta  = fmaf(gamma, boot[k], reward[k]) - values[k]      one fma, one subtraction
+ *   adv[k] = done[k, e] ? delta : fmaf(gl, carry, delta)
+ *   ret[k] = adv[k] + values[k]
+ *   carry  = adv[k]
+ * No output may alias an input. MACM_E_INVALID: any NULL pointer, a negative size. n_steps = 0 or
+ * E N = 0 does nothing.
+ */
+int macm_gae(const float* reward, const float* values, const float* boot, const uint8_t* done, int32_t n_steps,
+             int32_t n_envs, int32_t n_agents, float gamma, float lambda, float* adv, float* ret, void* stream);
+
 /* Observation of the current state without stepping (Flock.get_obs, mvmnt.py:181-222). */
 int macm_world_observe(macm_world* w, const macm_outputs* out, void* stream);
 

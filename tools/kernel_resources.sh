@@ -2,6 +2,8 @@
 # Per-kernel VGPRs, scratch bytes per lane and LDS bytes per block of the product TUs (compiler
 # remarks), one line per kernel:
 #   tools/kernel_resources.sh <dir holding csrc/>   (diff two trees to see what a change costs)
+# The policy and critic kernels are among them: the ObsPol / ObsPolV instantiations of the two rollout
+# units, and policy.hip's policy_flock_kernel, value_flock_kernel and gae_kernel.
 cd $1
 for f in csrc/flock_step_w64.hip csrc/flock_rollout_w64.hip csrc/flock_rollout_ar_w64.hip csrc/flock_step_wg.hip csrc/tdm_step_wg.hip csrc/policy.hip; do
   extra=""; case $f in csrc/flock_rollout_w64.hip|csrc/flock_rollout_ar_w64.hip) extra="-mllvm -disable-machine-licm";; esac
