@@ -1179,6 +1179,51 @@ int macm_gae(const float* reward, const float* values, const float* boot, const 
   return MACM_OK;
 }
 
+// The workspace of macm_policy_grad / macm_value_grad: one partial of the largest net per wave
+static int64_t mlp_grad_workspace_bytes(int64_t rows) {
+  return (int64_t)mlp_grad_partials(rows) * kGradMaxParams * (int64_t)sizeof(float);
+}
+
+int macm_mlp_grad_workspace(int64_t rows, int64_t* bytes) {
+  if (!bytes) return fail(MACM_E_INVALID, "grad: bytes is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "grad: rows must be >= 0");
+  *bytes = mlp_grad_workspace_bytes(rows);
+  return MACM_OK;
+}
+
+// What the two gradient calls share behind their struct checks
+static int mlp_grad(const float* params, int od, int hidden, int n_hidden, int n_out, const void* obs, int32_t obs_f64,
+                    int64_t rows, const float* dout, float* grad, void* workspace, int64_t workspace_bytes,
+                    void* stream) {
+  if (!obs || !dout || !grad) return fail(MACM_E_INVALID, "grad: obs/dout/grad is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "grad: rows must be >= 0");
+  if (rows > 0 && !workspace) return fail(MACM_E_INVALID, "grad: workspace is NULL");
+  if (rows > 0 && (reinterpret_cast<uintptr_t>(workspace) & 15))
+    return fail(MACM_E_INVALID, "grad: workspace must be 16-byte aligned");
+  if (rows > 0 && workspace_bytes < mlp_grad_workspace_bytes(rows))
+    return fail(MACM_E_INVALID, "grad: workspace_bytes " + std::to_string(workspace_bytes) + " is below the " +
+                                    std::to_string(mlp_grad_workspace_bytes(rows)) + " of macm_mlp_grad_workspace");
+  HIP_TRY(launch_mlp_grad(params, od, hidden, n_hidden, n_out, obs, obs_f64 != 0, rows, dout, grad, (float*)workspace,
+                          (hipStream_t)stream));
+  return MACM_OK;
+}
+
+int macm_policy_grad(const macm_policy_mlp* p, const void* obs, int32_t obs_f64, int64_t rows, const float* dlogits,
+                     float* grad, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!p) return fail(MACM_E_INVALID, "policy is NULL");
+  if (const int rc = policy_check(p)) return rc;
+  return mlp_grad(p->params, p->in_dim, p->hidden, p->n_hidden, kPolicyLogits, obs, obs_f64, rows, dlogits, grad,
+                  workspace, workspace_bytes, stream);
+}
+
+int macm_value_grad(const macm_value_mlp* c, const void* obs, int32_t obs_f64, int64_t rows, const float* dvalues,
+                    float* grad, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!c) return fail(MACM_E_INVALID, "critic is NULL");
+  if (const int rc = critic_check(c)) return rc;
+  return mlp_grad(c->params, c->in_dim, c->hidden, c->n_hidden, 1, obs, obs_f64, rows, dvalues, grad, workspace,
+                  workspace_bytes, stream);
+}
+
 int macm_world_observe(macm_world* w, const macm_outputs* out, void* stream) {
   if (!w || !out) return fail(MACM_E_INVALID, "world/out is NULL");
   DeviceGuard g(w->device);

@@ -1,0 +1,250 @@
+// policy_grad.hip — parameter gradients of the two MLPs (macm_policy_grad / macm_value_grad): from
+// dL/dout of every row to dL/dparams, one launch per net plus a small reduction.
+//
+// The definition (include/macm.h): the forward is policy_mlp.hpp's, bit for bit; with a_0 the float32
+// obs row, a_l the stored (post-relu) activation of hidden layer l and d_L = dout, from the last layer
+// to the first
+//   gW_l[k][j] = sum_r a_{l-1}[r][k] d_l[r][j]     gb_l[j] = sum_r d_l[r][j]
+//   d_{l-1}[r][k] = a_{l-1}[r][k] > 0 ? sum_j W_l[k][j] d_l[r][j] : 0
+// all float32. The sums' association is this file's, fixed by `rows` alone: no atomics anywhere.
+//
+// Per-row part (VALU): one wave per block, lane = row, tiles of 64 rows. The forward is recomputed with
+// policy_layer and scalar-loaded weights exactly as policy_mlp_row_t does, x, h1, h2 stay in registers;
+// each d_{l-1}[k] is the j-ordered fmaf chain from +0 over W_l[k][0..OUT), whose operands are again
+// wave-uniform (contiguous in j: wide scalar loads). Nothing per row goes to global memory.
+//
+// Weight gradients (MFMA): gW_l = A_{l-1}^T [in x 64] · D_l [64 x out], contracted over the tile's rows
+// with v_mfma_f32_32x32x2_f32 (exact f32, the k-ordered fmaf chain). Lane l supplies A[i = l & 31][k = l >> 5]
+// and B[k = l >> 5][j = l & 31], so both operands are read from row-major LDS images [64 rows][33] at
+// [row 2s + (l >> 5)][l & 31] for s = 0..31: 32 MFMAs per layer and tile into 16 accumulator registers that
+// live across all of the wave's tiles. The images are written lane = row (stride 33: conflict-free) and
+// only their first `in` / `out` columns; the MFMA reads all 32, and what it reads past them lands in
+// output rows / columns that are never stored (row i of the product depends on A's column i alone, column
+// j on B's column j alone). So H = 16, the 9 or 1 outputs and the 4 or 6 inputs use the 32 x 32 tile
+// partly empty rather than 16x16x4: one code path, and the MFMA pipe is not what limits this kernel.
+//
+// Bias gradients: gb_1 rides in the first layer's product as a ones column behind x (in + 1 <= 7 columns
+// of 32). The other layers' A operand may be full (H = 32), so gb_2 and gb_3 are lane-local float32 sums
+// over the wave's tiles, reduced once per wave at the end through LDS in lane order.
+//
+// Cross-wave reduction: P = min(tiles, kGradMaxPartials) waves; wave w takes tiles w, w + P, w + 2P, ...
+// (64-bit row indices) and writes one partial [n_params] to the caller's workspace. mlp_grad_reduce_kernel
+// sums the P partials per parameter in index order in float64 (four contiguous runs, then the four run
+// sums in order) and rounds once. A tail lane past `rows` loads nothing and carries x = 0, dout = 0: every
+// d of it is an exact zero and so is each of its products.
+#include "policy_mlp.hpp"
+
+namespace macm {
+
+using grad_f32x16 = __attribute__((ext_vector_type(16))) float;
+constexpr int kGradLds = 33;  // floats per row of an LDS operand image: 32 columns and one of padding
+
+// d_prev[k] = a[k] > 0 ? sum_j W[k][j] d[j] : 0, the sum as the j-ordered fmaf chain from +0; W wave-uniform
+template <int IN, int OUT>
+__device__ __forceinline__ void grad_back_layer(policy_cptr W, const float (&a)[IN], const float (&d)[OUT],
+                                                float (&dp)[IN]) {
+#pragma unroll
+  for (int k = 0; k < IN; ++k) {
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < OUT; ++j) s = __builtin_fmaf(W[k * OUT + j], d[j], s);
+    dp[k] = a[k] > 0.0f ? s : 0.0f;
+  }
+}
+
+// acc += a^T d over the tile's 64 rows: the lane's row of each operand into its LDS image, then 32 MFMAs
+template <int IN, int OUT>
+__device__ __forceinline__ void grad_outer(float* __restrict__ sA, float* __restrict__ sB, const float (&a)[IN],
+                                           const float (&d)[OUT], grad_f32x16& acc, int lane) {
+  static_assert(IN <= 32 && OUT <= 32, "one 32 x 32 block");
+  __syncthreads();  // the reads of the images' last use are done
+#pragma unroll
+  for (int k = 0; k < IN; ++k) sA[lane * kGradLds + k] = a[k];
+#pragma unroll
+  for (int j = 0; j < OUT; ++j) sB[lane * kGradLds + j] = d[j];
+  __syncthreads();
+  const int at = (lane >> 5) * kGradLds + (lane & 31);
+#pragma unroll
+  for (int s = 0; s < 32; ++s)
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sA[at + 2 * s * kGradLds], sB[at + 2 * s * kGradLds], acc, 0, 0, 0);
+}
+
+// The [IN x OUT] corner of a 32 x 32 accumulator block into dst[i * OUT + j]; register g of lane l holds
+// row (g & 3) + 8 (g >> 2) + 4 (l >> 5), column l & 31
+template <int IN, int OUT>
+__device__ __forceinline__ void grad_store_block(const grad_f32x16& acc, float* __restrict__ dst, int lane) {
+  const int j = lane & 31;
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int i = (g & 3) + 8 * (g >> 2) + 4 * (lane >> 5);
+    if (i < IN && j < OUT) dst[i * OUT + j] = acc[g];
+  }
+}
+
+// dst[j] = sum over lanes (in lane order) of b[j], through an LDS image
+template <int OUT>
+__device__ __forceinline__ void grad_store_bias(float* __restrict__ sm, const float (&b)[OUT], float* __restrict__ dst,
+                                                int lane) {
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < OUT; ++j) sm[lane * kGradLds + j] = b[j];
+  __syncthreads();
+  if (lane < OUT) {
+    float s = 0.0f;
+    for (int r = 0; r < 64; ++r) s = s + sm[r * kGradLds + lane];
+    dst[lane] = s;
+  }
+}
+
+template <typename OT, int OD, int H, int NH, int NOUT>
+__device__ __forceinline__ void mlp_grad_body(policy_cptr p, const OT* __restrict__ obs, long long rows,
+                                              const float* __restrict__ dout, float* __restrict__ part,
+                                              float* __restrict__ sA, float* __restrict__ sB) {
+  const int lane = threadIdx.x;
+  const long long tiles = (rows + 63) >> 6;
+  const policy_cptr W1 = p, b1 = W1 + OD * H;
+  const policy_cptr W2 = b1 + H, b2 = W2 + H * H;  // (NH == 2)
+  const policy_cptr W3 = NH == 2 ? b2 + H : b1 + H;  // (b3 is not read: the forward stops at the last hidden layer)
+  grad_f32x16 acc1, acc2, acc3;
+#pragma unroll
+  for (int g = 0; g < 16; ++g) acc1[g] = acc2[g] = acc3[g] = 0.0f;
+  float bs2[H], bs3[NOUT];
+#pragma unroll
+  for (int j = 0; j < H; ++j) bs2[j] = 0.0f;
+#pragma unroll
+  for (int j = 0; j < NOUT; ++j) bs3[j] = 0.0f;
+
+  for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const long long r = t * 64 + lane;
+    float x[OD], d3[NOUT];
+#pragma unroll
+    for (int q = 0; q < OD; ++q) x[q] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NOUT; ++j) d3[j] = 0.0f;
+    if (r < rows) {
+#pragma unroll
+      for (int q = 0; q < OD; ++q) x[q] = (float)obs[r * OD + q];
+#pragma unroll
+      for (int j = 0; j < NOUT; ++j) d3[j] = dout[r * NOUT + j];
+    }
+    float h1[H], dtop[H];
+    policy_layer<OD, H, true>(W1, b1, x, h1);
+    if constexpr (NH == 2) {
+      float h2[H];
+      policy_layer<H, H, true>(W2, b2, h1, h2);
+      grad_outer<H, NOUT>(sA, sB, h2, d3, acc3, lane);
+      grad_back_layer<H, NOUT>(W3, h2, d3, dtop);
+    } else {
+      grad_outer<H, NOUT>(sA, sB, h1, d3, acc3, lane);
+      grad_back_layer<H, NOUT>(W3, h1, d3, dtop);
+    }
+#pragma unroll
+    for (int j = 0; j < NOUT; ++j) bs3[j] = bs3[j] + d3[j];
+    float xs[OD + 1];  // x and the ones column that sums d1 into gb_1
+#pragma unroll
+    for (int q = 0; q < OD; ++q) xs[q] = x[q];
+    xs[OD] = 1.0f;
+    if constexpr (NH == 2) {
+      grad_outer<H, H>(sA, sB, h1, dtop, acc2, lane);
+#pragma unroll
+      for (int j = 0; j < H; ++j) bs2[j] = bs2[j] + dtop[j];
+      float d1[H];
+      grad_back_layer<H, H>(W2, h1, dtop, d1);
+      grad_outer<OD + 1, H>(sA, sB, xs, d1, acc1, lane);
+    } else {
+      grad_outer<OD + 1, H>(sA, sB, xs, dtop, acc1, lane);
+    }
+  }
+
+  // the wave's partial, in the layout of params: rows 0..OD-1 of the first block are W1, row OD is b1
+  grad_store_block<OD + 1, H>(acc1, part, lane);
+  float* o = part + OD * H + H;
+  if constexpr (NH == 2) {
+    grad_store_block<H, H>(acc2, o, lane);
+    grad_store_bias<H>(sA, bs2, o + H * H, lane);
+    o += H * H + H;
+  }
+  grad_store_block<H, NOUT>(acc3, o, lane);
+  grad_store_bias<NOUT>(sB, bs3, o + H * NOUT, lane);
+}
+
+// One wave per block; block b writes partial b. od, hidden and n_hidden are kernel arguments: the branches
+// are wave-uniform, each body fully unrolled, as policy_mlp_row's.
+template <typename OT, int NOUT>
+__global__ __launch_bounds__(64) void mlp_grad_kernel(const float* __restrict__ params, int od, int hidden,
+                                                      int n_hidden, const OT* __restrict__ obs, long long rows,
+                                                      const float* __restrict__ dout, float* __restrict__ partials,
+                                                      int n_params) {
+  __shared__ float sA[64 * kGradLds], sB[64 * kGradLds];
+  const policy_cptr p = (policy_cptr)(unsigned long long)params;
+  float* const part = partials + (size_t)blockIdx.x * n_params;
+#define MACM_GRAD_BODY(OD_, H_, NH_) mlp_grad_body<OT, OD_, H_, NH_, NOUT>(p, obs, rows, dout, part, sA, sB)
+  if (od == 6) {
+    if (hidden == 32) {
+      if (n_hidden == 2) MACM_GRAD_BODY(6, 32, 2); else MACM_GRAD_BODY(6, 32, 1);
+    } else {
+      if (n_hidden == 2) MACM_GRAD_BODY(6, 16, 2); else MACM_GRAD_BODY(6, 16, 1);
+    }
+  } else {
+    if (hidden == 32) {
+      if (n_hidden == 2) MACM_GRAD_BODY(4, 32, 2); else MACM_GRAD_BODY(4, 32, 1);
+    } else {
+      if (n_hidden == 2) MACM_GRAD_BODY(4, 16, 2); else MACM_GRAD_BODY(4, 16, 1);
+    }
+  }
+#undef MACM_GRAD_BODY
+}
+
+// grad[i] = the sum of partials[q][i] over q in index order: thread (run g, column c) sums the g-th
+// quarter of the partials in float64, then run 0's thread adds the four run sums in order and rounds once
+__global__ __launch_bounds__(256) void mlp_grad_reduce_kernel(const float* __restrict__ partials, int n_part,
+                                                              int n_params, float* __restrict__ grad) {
+  __shared__ double run[4][64];
+  const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int i = blockIdx.x * 64 + c;
+  const int per = (n_part + 3) >> 2;
+  const int lo = g * per, hi = lo + per < n_part ? lo + per : n_part;
+  double s = 0.0;
+  if (i < n_params) {
+#pragma unroll 8
+    for (int q = lo; q < hi; ++q) s = s + (double)partials[(size_t)q * n_params + i];
+  }
+  run[g][c] = s;
+  __syncthreads();
+  if (g == 0 && i < n_params) grad[i] = (float)(((run[0][c] + run[1][c]) + run[2][c]) + run[3][c]);
+}
+
+long long mlp_grad_partials(long long rows) {
+  const long long tiles = (rows + 63) / 64;
+  return tiles < kGradMaxPartials ? tiles : kGradMaxPartials;
+}
+
+hipError_t launch_mlp_grad(const float* params, int od, int hidden, int n_hidden, int n_out, const void* obs,
+                           bool obs_f64, long long rows, const float* dout, float* grad, float* workspace,
+                           hipStream_t s) {
+  const int n_params = od * hidden + hidden + (n_hidden == 2 ? hidden * hidden + hidden : 0) + hidden * n_out + n_out;
+  if (rows <= 0) return hipMemsetAsync(grad, 0, sizeof(float) * n_params, s);
+  const int P = (int)mlp_grad_partials(rows);
+  const dim3 grid((unsigned)P), block(64);
+  if (n_out == kPolicyLogits) {
+    if (obs_f64)
+      hipLaunchKernelGGL((mlp_grad_kernel<double, kPolicyLogits>), grid, block, 0, s, params, od, hidden, n_hidden,
+                         (const double*)obs, rows, dout, workspace, n_params);
+    else
+      hipLaunchKernelGGL((mlp_grad_kernel<float, kPolicyLogits>), grid, block, 0, s, params, od, hidden, n_hidden,
+                         (const float*)obs, rows, dout, workspace, n_params);
+  } else {
+    if (obs_f64)
+      hipLaunchKernelGGL((mlp_grad_kernel<double, 1>), grid, block, 0, s, params, od, hidden, n_hidden,
+                         (const double*)obs, rows, dout, workspace, n_params);
+    else
+      hipLaunchKernelGGL((mlp_grad_kernel<float, 1>), grid, block, 0, s, params, od, hidden, n_hidden,
+                         (const float*)obs, rows, dout, workspace, n_params);
+  }
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  hipLaunchKernelGGL(mlp_grad_reduce_kernel, dim3((unsigned)((n_params + 63) / 64)), dim3(256), 0, s, workspace, P,
+                     n_params, grad);
+  return hipGetLastError();
+}
+
+}  // namespace macm

@@ -163,4 +163,14 @@ hipError_t launch_gae(const float* reward, const float* values, const float* boo
 hipError_t launch_policy_flock(const PolicyArgs& M, const void* obs, bool obs_f64, int od, long long rows,
                                uint8_t* act, hipStream_t s);
 
+// host side, policy_grad.hip: dL/dparams of either net (n_out = 9: the policy, 1: the critic) from dout
+// [rows, n_out] (macm_policy_grad / macm_value_grad). One wave writes one partial [n_params] into the
+// workspace, at most kGradMaxPartials of them; kGradMaxParams bounds n_params over the supported shapes.
+constexpr int kGradMaxPartials = 2048;
+constexpr int kGradMaxParams = 6 * 32 + 32 + 32 * 32 + 32 + 32 * kPolicyLogits + kPolicyLogits;  // 1,577
+long long mlp_grad_partials(long long rows);  // min(ceil(rows / 64), kGradMaxPartials)
+hipError_t launch_mlp_grad(const float* params, int od, int hidden, int n_hidden, int n_out, const void* obs,
+                           bool obs_f64, long long rows, const float* dout, float* grad, float* workspace,
+                           hipStream_t s);
+
 }  // namespace macm

@@ -279,6 +279,11 @@ SIGNATURES = {
                                                      c_void_p, POINTER(MacmOutputs), c_void_p]),
     "macm_gae": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float,
                          c_void_p, c_void_p, c_void_p]),
+    "macm_mlp_grad_workspace": (c_int, [c_int64, POINTER(c_int64)]),
+    "macm_policy_grad": (c_int, [POINTER(MacmPolicyMlp), c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
+                                 c_int64, c_void_p]),
+    "macm_value_grad": (c_int, [POINTER(MacmValueMlp), c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
+                                c_int64, c_void_p]),
     "macm_bots_flock": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
     "macm_bots_combat": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
 }

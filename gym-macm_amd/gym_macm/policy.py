@@ -23,6 +23,17 @@ and ``gae`` turns a trajectory into advantages and returns in one launch:
     boot = torch.empty((K, E, N), device=dev)
     traj = vec.rollout_policy(acts, K, noise=g, trajectory=True, logits=lg, values=vals, boot=boot)
     adv, ret = gae(traj["reward"], vals[:K], boot, traj["done"], 0.99, 0.95)
+
+Learning on those rows stays in the library too: ``forward`` is the same kernel under torch.autograd,
+and its backward is one launch per net (macm_policy_grad / macm_value_grad), with no nn.Module copy
+of the net and no per-row activation kept:
+
+    pol.params.requires_grad_(True); crit.params.requires_grad_(True)
+    opt = torch.optim.Adam([pol.params, crit.params], lr=3e-4)
+    lg = pol.forward(traj["obs"])          # [..., 9], the bits rollout_policy stored at these params
+    v = crit.forward(traj["obs"])          # [...]
+    loss = ppo_loss(lg, old_logits, actions, adv, ret, v)   # the caller's torch code, any loss
+    loss.backward(); opt.step()            # params change in place: the next launch reads them
 """
 from __future__ import annotations
 
@@ -33,6 +44,8 @@ import torch
 from . import _abi
 
 N_LOGITS = 9
+GRAD_TILE_ROWS = 64  # macm_policy_grad / macm_value_grad: one wave sums tiles of this many rows ...
+GRAD_MAX_PARTIALS = 2048  # ... and at most this many waves write a partial (csrc/policy_mlp.hpp, kGradMaxPartials)
 
 
 def layer_shapes(in_dim: int, hidden: int, n_hidden: int, n_out: int = N_LOGITS) -> list:
@@ -83,7 +96,8 @@ class _Mlp:
             if tuple(w.shape) != (i, o) or tuple(b.shape) != (o,):
                 raise ValueError(f"layer shapes must be W [{i}, {o}] and b [{o}]; got {tuple(w.shape)}, {tuple(b.shape)}")
             flat += [w.detach().reshape(-1).to(self.device), b.detach().reshape(-1).to(self.device)]
-        self.params.copy_(torch.cat(flat))
+        with torch.no_grad():  # (params may be a leaf that requires grad: a learner's in-place write)
+            self.params.copy_(torch.cat(flat))
         return self
 
     def unpack(self):
@@ -100,6 +114,55 @@ class _Mlp:
         """The weights of torch.nn.Linear layers ([out, in] each), transposed to [in][out], into params."""
         return self.pack([l.weight.detach().t().contiguous() for l in layers], [l.bias.detach() for l in layers])
 
+    def _check_rows(self, obs: torch.Tensor):
+        if obs.device != self.device or not obs.is_contiguous() or obs.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"obs must be a contiguous float32/float64 tensor on the {self.WHAT}'s device")
+        if obs.shape[-1] != self.in_dim:
+            raise ValueError(f"obs rows must have {self.in_dim} values")
+        if obs.requires_grad:
+            raise ValueError(f"obs must not require grad (the {self.WHAT} has no gradient with respect to obs)")
+
+    def _outputs(self, obs: torch.Tensor) -> torch.Tensor:
+        """The net's outputs for obs through the one-shot kernel (the subclass's)."""
+        raise NotImplementedError
+
+    def forward(self, obs: torch.Tensor) -> torch.Tensor:
+        """The net's outputs for obs [..., in_dim] with the bits of the one-shot kernels and the rollouts;
+        where ``params.requires_grad`` is set (and grad mode is on) the result is differentiable with respect
+        to params: its backward is one launch of the gradient kernel, which recomputes the activations."""
+        self._check_rows(obs)
+        if self.params.requires_grad and torch.is_grad_enabled():
+            return _MlpForward.apply(self.params, obs, self)
+        return self._outputs(obs)
+
+    def grad_workspace_bytes(self, rows: int) -> int:
+        n = ctypes.c_int64(0)
+        _abi.check(_abi.lib().macm_mlp_grad_workspace(int(rows), ctypes.byref(n)), "macm_mlp_grad_workspace")
+        return int(n.value)
+
+    def param_grad(self, obs: torch.Tensor, dout: torch.Tensor) -> torch.Tensor:
+        """dL/dparams (float32 [n_params], a new tensor) from dout = dL/doutputs (float32 [..., 9]; a critic:
+        [...]) over obs [..., in_dim], on the current stream (macm_policy_grad / macm_value_grad). The
+        workspace is this object's and grows on demand: calls on one object belong on one stream."""
+        self._check_rows(obs)
+        lead = tuple(obs.shape[:-1])
+        want = lead + ((self.N_OUT,) if self.N_OUT != 1 else ())
+        if (dout.device != self.device or not dout.is_contiguous() or dout.dtype != torch.float32
+                or tuple(dout.shape) != want):
+            raise ValueError(f"dout must be a contiguous float32 {want} tensor on the {self.WHAT}'s device")
+        rows = obs.numel() // self.in_dim
+        need = self.grad_workspace_bytes(rows)
+        ws = getattr(self, "_grad_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._grad_ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=self.device)
+        grad = torch.empty_like(self.params, requires_grad=False)
+        with torch.cuda.device(self.device):
+            _abi.check(getattr(_abi.lib(), self.GRAD_FN)(
+                ctypes.byref(self._struct), ctypes.c_void_p(obs.data_ptr()), 1 if obs.dtype == torch.float64 else 0,
+                rows, ctypes.c_void_p(dout.data_ptr()), ctypes.c_void_p(grad.data_ptr()),
+                ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream(obs)), self.GRAD_FN)
+        return grad
+
     @classmethod
     def from_linear_layers(cls, layers, device=None):
         """layers: the hidden torch.nn.Linear layers (relu between them) and the head (9 logits; a critic: 1)."""
@@ -112,9 +175,33 @@ class _Mlp:
         return cls(layers[0].in_features, layers[0].out_features, len(layers) - 1, device).load_linear_layers(layers)
 
 
+class _MlpForward(torch.autograd.Function):
+    """net.forward(obs) as a function of net.params: the one-shot kernel forward, the gradient kernel backward.
+    Only obs is kept for the backward (and params, for autograd's check that they were not overwritten
+    between the two): the backward recomputes the activations from the params as they stand."""
+
+    @staticmethod
+    def forward(ctx, params, obs, net):
+        ctx.net = net
+        ctx.save_for_backward(params, obs)
+        return net._outputs(obs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        _, obs = ctx.saved_tensors
+        return ctx.net.param_grad(obs, gout.to(torch.float32).contiguous()), None, None
+
+
 class MlpPolicy(_Mlp):
     """in_dim: the world's obs_dim (4 polar, 6 cartesian); hidden 16 or 32; n_hidden 1 or 2."""
     N_OUT, STRUCT, WHAT = N_LOGITS, _abi.MacmPolicyMlp, "policy"
+    GRAD_FN = "macm_policy_grad"
+
+    def _outputs(self, obs: torch.Tensor) -> torch.Tensor:
+        logits = torch.empty(tuple(obs.shape[:-1]) + (N_LOGITS,), dtype=torch.float32, device=self.device)
+        self.act(obs, logits=logits)
+        return logits
 
     def act(self, obs: torch.Tensor, noise: torch.Tensor = None, logits: torch.Tensor = None,
             out: torch.Tensor = None) -> torch.Tensor:
@@ -147,6 +234,10 @@ class MlpCritic(_Mlp):
     """The critic beside the actor (macm_value_mlp): the same MLP with a trunk of its own and one output,
     V(obs). Its shape (hidden 16 or 32, n_hidden 1 or 2) is independent of the actor's."""
     N_OUT, STRUCT, WHAT = 1, _abi.MacmValueMlp, "critic"
+    GRAD_FN = "macm_value_grad"
+
+    def _outputs(self, obs: torch.Tensor) -> torch.Tensor:
+        return self.value(obs)
 
     def value(self, obs: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
         """V (float32 [...]) of obs [..., in_dim] (macm_value_flock)."""

@@ -610,6 +610,41 @@ int macm_world_rollout_policy_value_traj(macm_world* w, uint8_t* actions, int32_
 int macm_gae(const float* reward, const float* values, const float* boot, const uint8_t* done, int32_t n_steps,
              int32_t n_envs, int32_t n_agents, float gamma, float lambda, float* adv, float* ret, void* stream);
 
+/*
+ * Parameter gradients of the two MLPs: from dL/dout of every row to dL/dparams, so that a learner's
+ * update needs no copy of the net and keeps no per-row activation. The library stays loss-agnostic:
+ * the caller turns logits and values into a loss and supplies dout = dL/dlogits [rows, 9] or
+ * dL/dvalue [rows]. All arithmetic is float32.
+ *   The forward pass is macm_policy_mlp's / macm_value_mlp's as defined above, bit for bit. a_0 is the
+ *   float32 input row, a_l the stored (post-relu) activation of hidden layer l; layer l has weights
+ *   W_l[in][out], and d_L = dout for the last layer. For each layer, from the last to the first:
+ *     gW_l[k][j]    = sum over rows r of a_{l-1}[r][k] * d_l[r][j]
+ *     gb_l[j]       = sum over rows r of d_l[r][j]
+ *     d_{l-1}[r][k] = (a_{l-1}[r][k] > 0) ? sum_j W_l[k][j] * d_l[r][j] : 0        (l > 1 only)
+ *   The relu derivative is taken from the forward's own stored activation, so it is 0 for 0, -0 and
+ *   NaN. The association of the sums is not fixed, but the result depends only on the inputs and
+ *   `rows`, never on timing: no floating-point atomics, partial sums combined in a fixed order, so two
+ *   calls with the same arguments give the same bits.
+ *   grad has the layout of params (W then b, layer after layer) and is overwritten, not accumulated;
+ *   rows = 0 writes zeros. Non-finite inputs give unspecified results. There is no gradient with
+ *   respect to obs.
+ * The library holds no state for this: the caller owns the workspace (device memory, 16-byte aligned),
+ * of at least macm_mlp_grad_workspace(rows) bytes: enough for either net of any supported shape, a
+ * function of rows only, nondecreasing in rows and constant from 2048 * 64 rows on. Its contents after
+ * a call are unspecified; two calls in flight at once need a workspace each. Everything is ordered on
+ * `stream`. Additive: MACM_ABI_VERSION stays 9.
+ * MACM_E_INVALID, with a message and nothing launched: a NULL struct or one outside the supported
+ * shapes, reserved != 0, params NULL or misaligned, obs, dout or grad NULL, rows < 0, workspace NULL,
+ * misaligned or workspace_bytes too small while rows > 0; macm_mlp_grad_workspace: rows < 0 or bytes NULL.
+ */
+int macm_mlp_grad_workspace(int64_t rows, int64_t* bytes);
+int macm_policy_grad(const macm_policy_mlp* p, const void* obs, int32_t obs_f64, int64_t rows,
+                     const float* dlogits /* [rows, 9] */, float* grad /* [n_params] */, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+int macm_value_grad(const macm_value_mlp* c, const void* obs, int32_t obs_f64, int64_t rows,
+                    const float* dvalues /* [rows] */, float* grad /* [n_params] */, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
 /* Observation of the current state without stepping (Flock.get_obs, mvmnt.py:181-222). */
 int macm_world_observe(macm_world* w, const macm_outputs* out, void* stream);
 
