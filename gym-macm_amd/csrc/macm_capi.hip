@@ -14,6 +14,7 @@
 
 #include "flock_common.hpp"
 #include "policy_mlp.hpp"
+#include "ppo_row.hpp"
 #include "py_mt19937.hpp"
 #include "reward_threshold.h"
 
@@ -1222,6 +1223,127 @@ int macm_value_grad(const macm_value_mlp* c, const void* obs, int32_t obs_f64, i
   if (const int rc = critic_check(c)) return rc;
   return mlp_grad(c->params, c->in_dim, c->hidden, c->n_hidden, 1, obs, obs_f64, rows, dvalues, grad, workspace,
                   workspace_bytes, stream);
+}
+
+// ---- the PPO loss (ppo_row.hpp): one-shot kernels and loss-to-gradient launches ------------------------
+static bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+static int64_t align16(int64_t n) { return (n + 15) & ~(int64_t)15; }
+
+// The workspace of macm_ppo_loss / macm_ppo_grad: the gradient partials, and behind them one stat partial
+// per wave (macm_ppo_loss has at most as many blocks as macm_ppo_grad has waves)
+static int64_t ppo_stat_offset(int64_t rows) { return align16(mlp_grad_workspace_bytes(rows)); }
+static int64_t ppo_workspace_bytes(int64_t rows) {
+  return ppo_stat_offset(rows) + (int64_t)mlp_grad_partials(rows) * kPpoStatSlots * (int64_t)sizeof(double);
+}
+
+int macm_ppo_workspace(int64_t rows, int64_t* bytes) {
+  if (!bytes) return fail(MACM_E_INVALID, "ppo: bytes is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "ppo: rows must be >= 0");
+  *bytes = ppo_workspace_bytes(rows);
+  return MACM_OK;
+}
+
+int macm_policy_logp(const float* logits, const uint8_t* actions, int64_t rows, float* logp, float* entropy,
+                     void* stream) {
+  if (!logits || !actions || !logp) return fail(MACM_E_INVALID, "logp: logits/actions/logp is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "logp: rows must be >= 0");
+  if (misaligned(logits, 4) || misaligned(logp, 4) || misaligned(entropy, 4))
+    return fail(MACM_E_INVALID, "logp: logits, logp and entropy must be 4-byte aligned");
+  HIP_TRY(launch_policy_logp(logits, actions, rows, logp, entropy, (hipStream_t)stream));
+  return MACM_OK;
+}
+
+// What macm_ppo_loss and macm_ppo_grad check alike: the config, rows and the workspace
+static int ppo_check(const macm_ppo_config* cfg, int64_t rows, bool clipped_value, const double* stats,
+                     const void* workspace, int64_t workspace_bytes) {
+  if (!cfg) return fail(MACM_E_INVALID, "ppo: cfg is NULL");
+  if (!(cfg->clip > 0.0f)) return fail(MACM_E_INVALID, "ppo: clip must be > 0");
+  if (!(cfg->vf_coef >= 0.0f) || !(cfg->ent_coef >= 0.0f))
+    return fail(MACM_E_INVALID, "ppo: vf_coef and ent_coef must be >= 0");
+  if (clipped_value && !(cfg->vf_clip > 0.0f))
+    return fail(MACM_E_INVALID, "ppo: vf_clip must be > 0 where old_values is given");
+  for (int i = 0; i < 4; ++i)
+    if (cfg->reserved[i] != 0) return fail(MACM_E_INVALID, "ppo: reserved must be 0");
+  if (rows < 0) return fail(MACM_E_INVALID, "ppo: rows must be >= 0");
+  if (misaligned(stats, 8)) return fail(MACM_E_INVALID, "ppo: stats must be 8-byte aligned");
+  if (rows > 0 && !workspace) return fail(MACM_E_INVALID, "ppo: workspace is NULL");
+  if (rows > 0 && misaligned(workspace, 16)) return fail(MACM_E_INVALID, "ppo: workspace must be 16-byte aligned");
+  if (rows > 0 && workspace_bytes < ppo_workspace_bytes(rows))
+    return fail(MACM_E_INVALID, "ppo: workspace_bytes " + std::to_string(workspace_bytes) + " is below the " +
+                                    std::to_string(ppo_workspace_bytes(rows)) + " of macm_ppo_workspace");
+  return MACM_OK;
+}
+
+int macm_ppo_loss(const macm_ppo_config* cfg, int64_t rows, const float* logits, const uint8_t* actions,
+                  const float* old_logp, const float* adv, const float* values, const float* ret,
+                  const float* old_values, const float* scale, float* dlogits, float* dvalues, double* stats,
+                  void* workspace, int64_t workspace_bytes, void* stream) {
+  if (const int rc = ppo_check(cfg, rows, old_values != nullptr, stats, workspace, workspace_bytes)) return rc;
+  if (!logits && !values) return fail(MACM_E_INVALID, "ppo: logits and values are both NULL");
+  if (logits && (!actions || !old_logp || !adv))
+    return fail(MACM_E_INVALID, "ppo: actions/old_logp/adv is NULL where logits is given");
+  if (values && !ret) return fail(MACM_E_INVALID, "ppo: ret is NULL where values is given");
+  if (dlogits && !logits) return fail(MACM_E_INVALID, "ppo: dlogits is wanted but logits is NULL");
+  if (dvalues && !values) return fail(MACM_E_INVALID, "ppo: dvalues is wanted but values is NULL");
+  for (const void* p : {(const void*)logits, (const void*)old_logp, (const void*)adv, (const void*)values,
+                        (const void*)ret, (const void*)old_values, (const void*)scale, (const void*)dlogits,
+                        (const void*)dvalues})
+    if (misaligned(p, 4)) return fail(MACM_E_INVALID, "ppo: the float32 arrays must be 4-byte aligned");
+  const hipStream_t s = (hipStream_t)stream;
+  if (rows == 0) {
+    if (stats) HIP_TRY(hipMemsetAsync(stats, 0, 8 * sizeof(double), s));
+    return MACM_OK;
+  }
+  const PpoCfg c{cfg->clip, cfg->vf_coef, cfg->ent_coef, cfg->vf_clip};
+  double* const part = stats ? reinterpret_cast<double*>((char*)workspace + ppo_stat_offset(rows)) : nullptr;
+  const PpoLossArgs A{logits, actions, old_logp, adv, values, ret, old_values, scale, dlogits, dvalues, part, c};
+  HIP_TRY(launch_ppo_loss(A, rows, s));
+  if (stats)
+    HIP_TRY(launch_ppo_stats(part, (int)ppo_loss_partials(rows), rows, c, logits != nullptr, values != nullptr, stats, s));
+  return MACM_OK;
+}
+
+int macm_ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c, const void* obs,
+                  int32_t obs_f64, int64_t rows, const uint8_t* actions, const float* old_logp, const float* adv,
+                  const float* ret, const float* old_values, float* grad_policy, float* grad_value, double* stats,
+                  void* workspace, int64_t workspace_bytes, void* stream) {
+  if (const int rc = ppo_check(cfg, rows, c && old_values, stats, workspace, workspace_bytes)) return rc;
+  if (!p && !c) return fail(MACM_E_INVALID, "ppo: policy and critic are both NULL");
+  if (p) {
+    if (const int rc = policy_check(p)) return rc;
+    if (!actions || !old_logp || !adv || !grad_policy)
+      return fail(MACM_E_INVALID, "ppo: actions/old_logp/adv/grad_policy is NULL where the policy is given");
+  }
+  if (c) {
+    if (const int rc = critic_check(c)) return rc;
+    if (!ret || !grad_value) return fail(MACM_E_INVALID, "ppo: ret/grad_value is NULL where the critic is given");
+  }
+  if (p && c && p->in_dim != c->in_dim)
+    return fail(MACM_E_INVALID, "ppo: the policy's in_dim and the critic's differ (they read the same obs rows)");
+  if (!obs) return fail(MACM_E_INVALID, "ppo: obs is NULL");
+  for (const void* q : {(const void*)old_logp, (const void*)adv, (const void*)ret, (const void*)old_values,
+                        (const void*)grad_policy, (const void*)grad_value})
+    if (misaligned(q, 4)) return fail(MACM_E_INVALID, "ppo: the float32 arrays must be 4-byte aligned");
+  const hipStream_t s = (hipStream_t)stream;
+  const auto count = [](int od, int h, int nh, int no) { return od * h + h + (nh == 2 ? h * h + h : 0) + h * no + no; };
+  if (rows == 0) {
+    if (p) HIP_TRY(hipMemsetAsync(grad_policy, 0, sizeof(float) * count(p->in_dim, p->hidden, p->n_hidden, kPolicyLogits), s));
+    if (c) HIP_TRY(hipMemsetAsync(grad_value, 0, sizeof(float) * count(c->in_dim, c->hidden, c->n_hidden, 1), s));
+    if (stats) HIP_TRY(hipMemsetAsync(stats, 0, 8 * sizeof(double), s));
+    return MACM_OK;
+  }
+  const PpoCfg k{cfg->clip, cfg->vf_coef, cfg->ent_coef, cfg->vf_clip};
+  double* const part = stats ? reinterpret_cast<double*>((char*)workspace + ppo_stat_offset(rows)) : nullptr;
+  const PpoGradArgs G{actions, old_logp, adv, ret, c ? old_values : nullptr, k, 1.0 / (double)rows, part};
+  if (p)
+    HIP_TRY(launch_mlp_ppo_grad(p->params, p->in_dim, p->hidden, p->n_hidden, kPolicyLogits, obs, obs_f64 != 0, rows, G,
+                                grad_policy, (float*)workspace, s));
+  if (c)
+    HIP_TRY(launch_mlp_ppo_grad(c->params, c->in_dim, c->hidden, c->n_hidden, 1, obs, obs_f64 != 0, rows, G, grad_value,
+                                (float*)workspace, s));
+  if (stats)
+    HIP_TRY(launch_ppo_stats(part, (int)mlp_grad_partials(rows), rows, k, p != nullptr, c != nullptr, stats, s));
+  return MACM_OK;
 }
 
 int macm_world_observe(macm_world* w, const macm_outputs* out, void* stream) {

@@ -32,9 +32,26 @@
 // sums the P partials per parameter in index order in float64 (four contiguous runs, then the four run
 // sums in order) and rounds once. A tail lane past `rows` loads nothing and carries x = 0, dout = 0: every
 // d of it is an exact zero and so is each of its products.
+//
+// Loss-to-gradient launches (macm_ppo_grad): the same body with DoutPpo in the place of DoutMem. The forward
+// goes on through the last layer (policy_layer with b3: the bits of macm_policy_mlp / macm_value_mlp) and
+// d_L of the lane's row is ppo_row.hpp's ppo_policy_row / ppo_value_row of those outputs, so neither the
+// logits nor dL/dlogits exist in memory; everything after d_L is the code above. The row's stat terms are
+// lane-local float64 sums over the wave's tiles, reduced once per wave through LDS in lane order into the
+// wave's stat partial. A tail lane's d_L is zero and it adds nothing to the stats.
 #include "policy_mlp.hpp"
+#include "ppo_row.hpp"
 
 namespace macm {
+
+// Where d_L comes from: the caller's dout [rows, NOUT], or the PPO loss of the forward's own outputs
+struct DoutMem {
+  static constexpr bool kMem = true;  // (the body's dout argument)
+};
+struct DoutPpo {
+  static constexpr bool kMem = false;
+  PpoGradArgs G;
+};
 
 using grad_f32x16 = __attribute__((ext_vector_type(16))) float;
 constexpr int kGradLds = 33;  // floats per row of an LDS operand image: 32 columns and one of padding
@@ -96,15 +113,49 @@ __device__ __forceinline__ void grad_store_bias(float* __restrict__ sm, const fl
   }
 }
 
-template <typename OT, int OD, int H, int NH, int NOUT>
+// d3 and the stat terms of the lane's row r from the last hidden activation: the output layer, then the loss
+template <int H, int NOUT>
+__device__ __forceinline__ void grad_ppo_dout(policy_cptr W3, policy_cptr b3, const float (&h)[H], long long r,
+                                              long long rows, const PpoGradArgs& G, float (&d3)[NOUT],
+                                              double (&st)[kPpoPolicyTerms]) {
+  float y[NOUT];
+  policy_layer<H, NOUT, false>(W3, b3, h, y);
+  if (r < rows) {
+    if constexpr (NOUT == kPolicyLogits) {
+      uint8_t a[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) a[q] = G.actions[r * 3 + q];
+      PpoPolicyTerms T;
+      ppo_policy_row(y, a, G.old_logp[r], G.adv[r], G.cfg, G.k, d3, T);
+      st[kPpoPl] = st[kPpoPl] + T.pl;
+      st[kPpoH] = st[kPpoH] + T.H;
+      st[kPpoKl] = st[kPpoKl] + T.kl;
+      st[kPpoClipped] = st[kPpoClipped] + T.clipped;
+      st[kPpoRatioMax] = T.ratio > st[kPpoRatioMax] ? T.ratio : st[kPpoRatioMax];
+    } else {
+      double vl;
+      d3[0] = ppo_value_row(y[0], G.ret[r], G.old_values != nullptr, G.old_values ? G.old_values[r] : 0.0f, G.cfg,
+                            G.k, vl);
+      st[0] = st[0] + vl;
+    }
+  }
+}
+
+template <typename OT, int OD, int H, int NH, int NOUT, typename Src = DoutMem>
 __device__ __forceinline__ void mlp_grad_body(policy_cptr p, const OT* __restrict__ obs, long long rows,
                                               const float* __restrict__ dout, float* __restrict__ part,
-                                              float* __restrict__ sA, float* __restrict__ sB) {
+                                              float* __restrict__ sA, float* __restrict__ sB, const Src& src = Src{}) {
   const int lane = threadIdx.x;
   const long long tiles = (rows + 63) >> 6;
   const policy_cptr W1 = p, b1 = W1 + OD * H;
   const policy_cptr W2 = b1 + H, b2 = W2 + H * H;  // (NH == 2)
-  const policy_cptr W3 = NH == 2 ? b2 + H : b1 + H;  // (b3 is not read: the forward stops at the last hidden layer)
+  const policy_cptr W3 = NH == 2 ? b2 + H : b1 + H;  // (DoutMem: b3 is not read, the forward stops at the last hidden layer)
+  [[maybe_unused]] const policy_cptr b3 = W3 + H * NOUT;
+  [[maybe_unused]] double st[kPpoPolicyTerms];  // DoutPpo: the wave's stat terms (the critic: st[0] alone)
+  if constexpr (!Src::kMem) {
+#pragma unroll
+    for (int q = 0; q < kPpoPolicyTerms; ++q) st[q] = 0.0;
+  }
   grad_f32x16 acc1, acc2, acc3;
 #pragma unroll
   for (int g = 0; g < 16; ++g) acc1[g] = acc2[g] = acc3[g] = 0.0f;
@@ -124,17 +175,21 @@ __device__ __forceinline__ void mlp_grad_body(policy_cptr p, const OT* __restric
     if (r < rows) {
 #pragma unroll
       for (int q = 0; q < OD; ++q) x[q] = (float)obs[r * OD + q];
+      if constexpr (Src::kMem) {
 #pragma unroll
-      for (int j = 0; j < NOUT; ++j) d3[j] = dout[r * NOUT + j];
+        for (int j = 0; j < NOUT; ++j) d3[j] = dout[r * NOUT + j];
+      }
     }
     float h1[H], dtop[H];
     policy_layer<OD, H, true>(W1, b1, x, h1);
     if constexpr (NH == 2) {
       float h2[H];
       policy_layer<H, H, true>(W2, b2, h1, h2);
+      if constexpr (!Src::kMem) grad_ppo_dout<H, NOUT>(W3, b3, h2, r, rows, src.G, d3, st);
       grad_outer<H, NOUT>(sA, sB, h2, d3, acc3, lane);
       grad_back_layer<H, NOUT>(W3, h2, d3, dtop);
     } else {
+      if constexpr (!Src::kMem) grad_ppo_dout<H, NOUT>(W3, b3, h1, r, rows, src.G, d3, st);
       grad_outer<H, NOUT>(sA, sB, h1, d3, acc3, lane);
       grad_back_layer<H, NOUT>(W3, h1, d3, dtop);
     }
@@ -166,6 +221,24 @@ __device__ __forceinline__ void mlp_grad_body(policy_cptr p, const OT* __restric
   }
   grad_store_block<H, NOUT>(acc3, o, lane);
   grad_store_bias<NOUT>(sB, bs3, o + H * NOUT, lane);
+
+  if constexpr (!Src::kMem) {  // the wave's stat partial: term q's 64 lane sums in lane order, by lane q
+    if (!src.G.stat) return;  // (wave-uniform: the caller wants no stats)
+    constexpr int NS = NOUT == kPolicyLogits ? kPpoPolicyTerms : 1;
+    double* const sd = reinterpret_cast<double*>(sA);  // (the kernel aligns sA; 5 x 64 doubles of its 8,448 bytes)
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NS; ++q) sd[q * 64 + lane] = st[q];
+    __syncthreads();
+    if (lane < NS) {
+      double s = 0.0;
+      for (int l = 0; l < 64; ++l) {
+        const double t = sd[lane * 64 + l];
+        s = (NOUT == kPolicyLogits && lane == kPpoRatioMax) ? (t > s ? t : s) : s + t;
+      }
+      src.G.stat[(size_t)blockIdx.x * kPpoStatSlots + (NOUT == kPolicyLogits ? lane : kPpoVl)] = s;
+    }
+  }
 }
 
 // One wave per block; block b writes partial b. od, hidden and n_hidden are kernel arguments: the branches
@@ -179,6 +252,35 @@ __global__ __launch_bounds__(64) void mlp_grad_kernel(const float* __restrict__ 
   const policy_cptr p = (policy_cptr)(unsigned long long)params;
   float* const part = partials + (size_t)blockIdx.x * n_params;
 #define MACM_GRAD_BODY(OD_, H_, NH_) mlp_grad_body<OT, OD_, H_, NH_, NOUT>(p, obs, rows, dout, part, sA, sB)
+  if (od == 6) {
+    if (hidden == 32) {
+      if (n_hidden == 2) MACM_GRAD_BODY(6, 32, 2); else MACM_GRAD_BODY(6, 32, 1);
+    } else {
+      if (n_hidden == 2) MACM_GRAD_BODY(6, 16, 2); else MACM_GRAD_BODY(6, 16, 1);
+    }
+  } else {
+    if (hidden == 32) {
+      if (n_hidden == 2) MACM_GRAD_BODY(4, 32, 2); else MACM_GRAD_BODY(4, 32, 1);
+    } else {
+      if (n_hidden == 2) MACM_GRAD_BODY(4, 16, 2); else MACM_GRAD_BODY(4, 16, 1);
+    }
+  }
+#undef MACM_GRAD_BODY
+}
+
+// The same launch with the PPO loss in the place of dout (macm_ppo_grad); block b also writes stat partial b
+template <typename OT, int NOUT>
+__global__ __launch_bounds__(64) void mlp_ppo_grad_kernel(const float* __restrict__ params, int od, int hidden,
+                                                          int n_hidden, const OT* __restrict__ obs, long long rows,
+                                                          const PpoGradArgs G, float* __restrict__ partials,
+                                                          int n_params) {
+  __shared__ __attribute__((aligned(16))) float sA[64 * kGradLds];
+  __shared__ float sB[64 * kGradLds];
+  const policy_cptr p = (policy_cptr)(unsigned long long)params;
+  float* const part = partials + (size_t)blockIdx.x * n_params;
+  const DoutPpo src{G};
+#define MACM_GRAD_BODY(OD_, H_, NH_) \
+  mlp_grad_body<OT, OD_, H_, NH_, NOUT, DoutPpo>(p, obs, rows, nullptr, part, sA, sB, src)
   if (od == 6) {
     if (hidden == 32) {
       if (n_hidden == 2) MACM_GRAD_BODY(6, 32, 2); else MACM_GRAD_BODY(6, 32, 1);
@@ -240,6 +342,34 @@ hipError_t launch_mlp_grad(const float* params, int od, int hidden, int n_hidden
     else
       hipLaunchKernelGGL((mlp_grad_kernel<float, 1>), grid, block, 0, s, params, od, hidden, n_hidden,
                          (const float*)obs, rows, dout, workspace, n_params);
+  }
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  hipLaunchKernelGGL(mlp_grad_reduce_kernel, dim3((unsigned)((n_params + 63) / 64)), dim3(256), 0, s, workspace, P,
+                     n_params, grad);
+  return hipGetLastError();
+}
+
+// launch_mlp_grad with the loss in the launch; rows > 0 (the caller serves rows = 0)
+hipError_t launch_mlp_ppo_grad(const float* params, int od, int hidden, int n_hidden, int n_out, const void* obs,
+                               bool obs_f64, long long rows, const PpoGradArgs& G, float* grad, float* workspace,
+                               hipStream_t s) {
+  const int n_params = od * hidden + hidden + (n_hidden == 2 ? hidden * hidden + hidden : 0) + hidden * n_out + n_out;
+  const int P = (int)mlp_grad_partials(rows);
+  const dim3 grid((unsigned)P), block(64);
+  if (n_out == kPolicyLogits) {
+    if (obs_f64)
+      hipLaunchKernelGGL((mlp_ppo_grad_kernel<double, kPolicyLogits>), grid, block, 0, s, params, od, hidden, n_hidden,
+                         (const double*)obs, rows, G, workspace, n_params);
+    else
+      hipLaunchKernelGGL((mlp_ppo_grad_kernel<float, kPolicyLogits>), grid, block, 0, s, params, od, hidden, n_hidden,
+                         (const float*)obs, rows, G, workspace, n_params);
+  } else {
+    if (obs_f64)
+      hipLaunchKernelGGL((mlp_ppo_grad_kernel<double, 1>), grid, block, 0, s, params, od, hidden, n_hidden,
+                         (const double*)obs, rows, G, workspace, n_params);
+    else
+      hipLaunchKernelGGL((mlp_ppo_grad_kernel<float, 1>), grid, block, 0, s, params, od, hidden, n_hidden,
+                         (const float*)obs, rows, G, workspace, n_params);
   }
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   hipLaunchKernelGGL(mlp_grad_reduce_kernel, dim3((unsigned)((n_params + 63) / 64)), dim3(256), 0, s, workspace, P,

@@ -96,6 +96,13 @@ class MacmValueMlp(Structure):
                 ("params", c_void_p)]
 
 
+class MacmPpoConfig(Structure):
+    """macm_ppo_config: the clip range, the coefficients of the value loss and of the entropy bonus, and the
+    value clip range (read only where old values are given); reserved is 0."""
+    _fields_ = [("clip", c_float), ("vf_coef", c_float), ("ent_coef", c_float), ("vf_clip", c_float),
+                ("reserved", c_int32 * 4)]
+
+
 class MacmState(Structure):
     _fields_ = [(n, c_void_p) for n in (
         "pos", "vel", "angle", "fat", "sleep", "targets", "contact_count", "contact_ab",
@@ -284,6 +291,11 @@ SIGNATURES = {
                                  c_int64, c_void_p]),
     "macm_value_grad": (c_int, [POINTER(MacmValueMlp), c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
                                 c_int64, c_void_p]),
+    "macm_policy_logp": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "macm_ppo_workspace": (c_int, [c_int64, POINTER(c_int64)]),
+    "macm_ppo_loss": (c_int, [POINTER(MacmPpoConfig), c_int64] + [c_void_p] * 12 + [c_int64, c_void_p]),
+    "macm_ppo_grad": (c_int, [POINTER(MacmPpoConfig), POINTER(MacmPolicyMlp), POINTER(MacmValueMlp), c_void_p, c_int32,
+                              c_int64] + [c_void_p] * 9 + [c_int64, c_void_p]),
     "macm_bots_flock": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
     "macm_bots_combat": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
 }

@@ -34,6 +34,9 @@ of the net and no per-row activation kept:
     v = crit.forward(traj["obs"])          # [...]
     loss = ppo_loss(lg, old_logits, actions, adv, ret, v)   # the caller's torch code, any loss
     loss.backward(); opt.step()            # params change in place: the next launch reads them
+
+The clipped PPO loss itself on the device, composed with ``forward`` or fused into the gradient launches,
+is in gym_macm.ppo (``log_prob``, ``ppo_loss``, ``ppo_grads``).
 """
 from __future__ import annotations
 

@@ -1,0 +1,240 @@
+"""The clipped PPO loss on device (include/macm.h, macm_ppo_loss): log-probabilities from stored logits, the
+loss under torch.autograd, and the loss fused into the gradient launches.
+
+    old_logp = ppo.log_prob(lg, traj_actions)              # once, from the logits rollout_policy stored
+    pol.params.requires_grad_(True); crit.params.requires_grad_(True)
+    # composed with the forward kernels: logits and dL/dlogits exist, nothing else per row is kept
+    loss, stats = ppo.ppo_loss(pol.forward(obs), crit.forward(obs), actions, old_logp, adv, ret)
+    loss.backward()
+    # or fused: neither the logits nor dL/dlogits exist in memory, one launch per net
+    stats = ppo.ppo_grads(pol, crit, obs, actions, old_logp, adv, ret)   # accumulates into params.grad
+    opt.step()
+
+``stats`` is a float64 [8] device tensor: loss, policy_loss, value_loss, entropy, approx_kl, clip_frac,
+ratio_max, rows. In the first epoch, with ``old_logp`` from ``log_prob`` on the rollout's own logits, the
+ratio is exactly 1, approx_kl 0 and clip_frac 0. The means are over the rows of the call: a minibatch is a
+contiguous slice of the leading dimension, and advantage normalisation is the caller's.
+
+The per-row definition is float64 on the float32 inputs (include/macm.h). There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from . import _abi
+from .policy import N_LOGITS, _overlap, _stream
+
+STATS = ("loss", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_frac", "ratio_max", "rows")
+
+_ws = {}  # device -> the workspace of ppo_loss on that device, grown on demand: calls belong on one stream
+
+
+def config(clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.01, vf_clip: float = None):
+    """The macm_ppo_config of these coefficients (vf_clip None: 0, read only where old values are given)."""
+    return _abi.MacmPpoConfig(float(clip), float(vf_coef), float(ent_coef), 0.0 if vf_clip is None else float(vf_clip),
+                              (ctypes.c_int32 * 4)(0, 0, 0, 0))
+
+
+def workspace_bytes(rows: int) -> int:
+    n = ctypes.c_int64(0)
+    _abi.check(_abi.lib().macm_ppo_workspace(int(rows), ctypes.byref(n)), "macm_ppo_workspace")
+    return int(n.value)
+
+
+def _workspace(owner, rows, device):
+    """The workspace for `rows` rows: the owner's (a net's, shared with param_grad) or this module's."""
+    need = workspace_bytes(rows)
+    ws = _ws.get(device) if owner is None else getattr(owner, "_grad_ws", None)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=device)
+        if owner is None:
+            _ws[device] = ws
+        else:
+            owner._grad_ws = ws
+    return ws
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _check(name, t, dev, dtype, shape):
+    if t.device != dev or not t.is_contiguous() or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} {tuple(shape)} tensor on {dev}")
+
+
+def _check_rows(dev, lead, actions, old_logp, adv, ret, old_values, policy: bool, value: bool):
+    """The per-row inputs behind the logits / values (or the obs rows): what each half reads must be there."""
+    if policy:
+        for name, t in (("actions", actions), ("old_logp", old_logp), ("adv", adv)):
+            if t is None:
+                raise ValueError(f"{name} is needed with the policy's logits")
+        _check("actions", actions, dev, torch.uint8, lead + (3,))
+        _check("old_logp", old_logp, dev, torch.float32, lead)
+        _check("adv", adv, dev, torch.float32, lead)
+    if value:
+        if ret is None:
+            raise ValueError("ret is needed with the critic's values")
+        _check("ret", ret, dev, torch.float32, lead)
+        if old_values is not None:
+            _check("old_values", old_values, dev, torch.float32, lead)
+    for name, t in (("old_logp", old_logp), ("adv", adv), ("ret", ret), ("old_values", old_values)):
+        if t is not None and t.requires_grad:
+            raise ValueError(f"{name} must not require grad (the loss is differentiable in logits and values only)")
+    if dev.type != "cuda":
+        raise ValueError("the PPO loss runs on a GPU device (no CPU fallback)")
+
+
+def _check_cfg(clip, vf_coef, ent_coef, vf_clip, old_values):
+    if not clip > 0 or not vf_coef >= 0 or not ent_coef >= 0:
+        raise ValueError("clip must be > 0, vf_coef and ent_coef >= 0")
+    if old_values is not None and (vf_clip is None or not vf_clip > 0):
+        raise ValueError("old_values needs vf_clip > 0")
+    if old_values is None and vf_clip is not None:
+        raise ValueError("vf_clip needs old_values")
+
+
+def log_prob(logits: torch.Tensor, actions: torch.Tensor, entropy: torch.Tensor = None) -> torch.Tensor:
+    """logp (float32 [...]): the log-probability of actions (uint8 [..., 3]) under logits (float32 [..., 9]),
+    in one launch (macm_policy_logp); entropy: float32 [...] or None, written with each row's entropy."""
+    dev = logits.device
+    if dev.type != "cuda":
+        raise ValueError("log_prob runs on a GPU device (no CPU fallback)")
+    if logits.dim() < 1 or logits.shape[-1] != N_LOGITS:
+        raise ValueError(f"logits rows must have {N_LOGITS} values")
+    lead = tuple(logits.shape[:-1])
+    _check("logits", logits, dev, torch.float32, lead + (N_LOGITS,))
+    _check("actions", actions, dev, torch.uint8, lead + (3,))
+    if entropy is not None:
+        _check("entropy", entropy, dev, torch.float32, lead)
+        if _overlap(entropy, logits) or _overlap(entropy, actions):
+            raise ValueError("entropy must not alias an input")
+    logp = torch.empty(lead, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(_abi.lib().macm_policy_logp(_p(logits.detach()), _p(actions), logits.numel() // N_LOGITS, _p(logp),
+                                               _p(entropy), _stream(logits)), "macm_policy_logp")
+    return logp
+
+
+def _launch_loss(cfg, rows, dev, logits, actions, old_logp, adv, values, ret, old_values, scale, dlogits, dvalues,
+                 stats):
+    ws = _workspace(None, rows, dev)
+    with torch.cuda.device(dev):
+        _abi.check(_abi.lib().macm_ppo_loss(ctypes.byref(cfg), rows, _p(logits), _p(actions), _p(old_logp), _p(adv),
+                                            _p(values), _p(ret), _p(old_values), _p(scale), _p(dlogits), _p(dvalues),
+                                            _p(stats), _p(ws), ws.numel(),
+                                            ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                   "macm_ppo_loss")
+
+
+class _PpoLoss(torch.autograd.Function):
+    """(loss, stats) as a function of logits and values: the forward is a stats-only launch, the backward one
+    launch that writes dL/dlogits and dL/dvalues with `scale` pointing at the incoming gradient. Only the
+    inputs are kept."""
+
+    @staticmethod
+    def forward(ctx, logits, values, actions, old_logp, adv, ret, old_values, cfg):
+        first = logits if logits is not None else values
+        dev = first.device
+        rows = first.numel() // (N_LOGITS if logits is not None else 1)
+        stats = torch.empty((8,), dtype=torch.float64, device=dev)
+        _launch_loss(cfg, rows, dev, logits, actions, old_logp, adv, values, ret, old_values, None, None, None, stats)
+        ctx.cfg, ctx.rows, ctx.dev = cfg, rows, dev
+        ctx.has = (logits is not None, values is not None, old_values is not None)
+        ctx.save_for_backward(*[t for t in (logits, values, actions, old_logp, adv, ret, old_values) if t is not None])
+        ctx.mark_non_differentiable(stats)
+        return stats[0].to(torch.float32), stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gloss, _gstats):
+        saved = list(ctx.saved_tensors)
+        has_l, has_v, has_o = ctx.has
+        logits = saved.pop(0) if has_l else None
+        values = saved.pop(0) if has_v else None
+        actions, old_logp, adv = (saved.pop(0), saved.pop(0), saved.pop(0)) if has_l else (None, None, None)
+        ret = saved.pop(0) if has_v else None
+        old_values = saved.pop(0) if has_o else None
+        want_l = has_l and ctx.needs_input_grad[0]
+        want_v = has_v and ctx.needs_input_grad[1]
+        dlogits = torch.empty_like(logits) if want_l else None
+        dvalues = torch.empty_like(values) if want_v else None
+        if (want_l or want_v) and ctx.rows > 0:
+            scale = gloss.to(torch.float32).reshape(1).contiguous()  # stays on the device: no synchronise
+            _launch_loss(ctx.cfg, ctx.rows, ctx.dev, logits if want_l else None, actions, old_logp, adv,
+                         values if want_v else None, ret, old_values if want_v else None, scale, dlogits, dvalues, None)
+        return dlogits, dvalues, None, None, None, None, None, None
+
+
+def ppo_loss(logits: torch.Tensor, values: torch.Tensor, actions: torch.Tensor, old_logp: torch.Tensor,
+             adv: torch.Tensor, ret: torch.Tensor, old_values: torch.Tensor = None, clip: float = 0.2,
+             vf_coef: float = 0.5, ent_coef: float = 0.01, vf_clip: float = None):
+    """(loss, stats): the clipped PPO loss of logits (float32 [..., 9]) and values (float32 [...]) over actions
+    (uint8 [..., 3]), old_logp, adv and ret (float32 [...]); old_values with vf_clip selects the clipped value
+    loss. loss is a float32 scalar, differentiable in logits and values (it composes with MlpPolicy.forward /
+    MlpCritic.forward); stats is float64 [8] (STATS). Either of logits and values may be None: that half of the
+    loss is left out."""
+    if logits is None and values is None:
+        raise ValueError("logits and values are both None")
+    _check_cfg(clip, vf_coef, ent_coef, vf_clip, old_values if values is not None else None)
+    if logits is not None:
+        if logits.dim() < 1 or logits.shape[-1] != N_LOGITS:
+            raise ValueError(f"logits rows must have {N_LOGITS} values")
+        dev, lead = logits.device, tuple(logits.shape[:-1])
+        _check("logits", logits, dev, torch.float32, lead + (N_LOGITS,))
+    else:
+        dev, lead = values.device, tuple(values.shape)
+    if values is not None:
+        _check("values", values, dev, torch.float32, lead)
+    _check_rows(dev, lead, actions, old_logp, adv, ret, old_values, logits is not None, values is not None)
+    if actions is not None and actions.requires_grad:
+        raise ValueError("actions must not require grad")
+    cfg = config(clip, vf_coef, ent_coef, vf_clip)
+    if values is None:
+        ret = old_values = None
+    if logits is None:
+        actions = old_logp = adv = None
+    return _PpoLoss.apply(logits, values, actions, old_logp, adv, ret, old_values, cfg)
+
+
+def ppo_grads(pol, crit, obs: torch.Tensor, actions: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor,
+              ret: torch.Tensor, old_values: torch.Tensor = None, clip: float = 0.2, vf_coef: float = 0.5,
+              ent_coef: float = 0.01, vf_clip: float = None) -> torch.Tensor:
+    """stats (float64 [8]) of the clipped PPO loss of pol (an MlpPolicy) and crit (an MlpCritic) over obs
+    [..., in_dim], with dL/dparams accumulated into pol.params.grad and crit.params.grad exactly as
+    ``ppo_loss(pol.forward(obs), crit.forward(obs), ...)[0].backward()`` would, bit for bit, but with the loss
+    inside the gradient launches (macm_ppo_grad): no logits, values or their gradients in memory. Either net
+    may be None. The workspace is the first net's and grows on demand: calls on one object belong on one
+    stream."""
+    if pol is None and crit is None:
+        raise ValueError("pol and crit are both None")
+    first = pol if pol is not None else crit
+    if pol is not None and crit is not None and (pol.device != crit.device or pol.in_dim != crit.in_dim):
+        raise ValueError("the policy and the critic must share a device and in_dim (they read the same obs rows)")
+    _check_cfg(clip, vf_coef, ent_coef, vf_clip, old_values if crit is not None else None)
+    first._check_rows(obs)
+    dev, lead = first.device, tuple(obs.shape[:-1])
+    _check_rows(dev, lead, actions, old_logp, adv, ret, old_values, pol is not None, crit is not None)
+    rows = obs.numel() // first.in_dim
+    cfg = config(clip, vf_coef, ent_coef, vf_clip)
+    ws = _workspace(first, rows, dev)
+    gp = torch.empty_like(pol.params, requires_grad=False) if pol is not None else None
+    gv = torch.empty_like(crit.params, requires_grad=False) if crit is not None else None
+    stats = torch.empty((8,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(_abi.lib().macm_ppo_grad(
+            ctypes.byref(cfg), ctypes.byref(pol.struct()) if pol is not None else None,
+            ctypes.byref(crit.struct()) if crit is not None else None, _p(obs), 1 if obs.dtype == torch.float64 else 0,
+            rows, _p(actions) if pol is not None else None, _p(old_logp) if pol is not None else None,
+            _p(adv) if pol is not None else None, _p(ret) if crit is not None else None,
+            _p(old_values) if crit is not None else None, _p(gp), _p(gv), _p(stats), _p(ws), ws.numel(), _stream(obs)),
+            "macm_ppo_grad")
+    for net, g in ((pol, gp), (crit, gv)):
+        if net is not None:
+            if net.params.grad is None:
+                net.params.grad = g
+            else:
+                net.params.grad.add_(g)
+    return stats

@@ -645,6 +645,83 @@ int macm_value_grad(const macm_value_mlp* c, const void* obs, int32_t obs_f64, i
                     const float* dvalues /* [rows] */, float* grad /* [n_params] */, void* workspace,
                     int64_t workspace_bytes, void* stream);
 
+/*
+ * The clipped PPO loss on device: from logits and values (or, in macm_ppo_grad, from obs rows) to
+ * dL/dlogits, dL/dvalue (dL/dparams) and the statistics, so that an update pass keeps nothing per row
+ * but its inputs. The loss-agnostic path above stays; this is one particular loss, defined so that it
+ * can be checked. All per-row arithmetic is float64 on the float32 inputs, every operation rounded
+ * once, in the association written here; every stored float32 is one rounding of a float64 value.
+ * Row r has heads h = 0..2 of MultiDiscrete([3, 3, 3]), z = logits[r], a_h = actions[r][h] (0, 1 or 2):
+ *   m_h = max_c z[3h+c]; e_c = exp(z[3h+c] - m_h); S_h = (e_0 + e_1) + e_2; lse_h = m_h + log S_h
+ *   lp_hc = z[3h+c] - lse_h; p_hc = e_c / S_h
+ *   logp = (lp_0a0 + lp_1a1) + lp_2a2; logp32 = (float)logp       what macm_policy_logp stores
+ *   H_h = -((p_h0 lp_h0 + p_h1 lp_h1) + p_h2 lp_h2); H = (H_0 + H_1) + H_2     (macm_policy_logp: (float)H)
+ *   ratio = exp((double)logp32 - (double)old_logp)
+ *     logp is rounded to float32 before the subtraction, so an old_logp that macm_policy_logp stored
+ *     from the same logits gives ratio = 1 exactly; the derivative treats that rounding as the identity.
+ *   s1 = ratio adv; s2 = min(max(ratio, 1 - clip), 1 + clip) adv; pl = -min(s1, s2)
+ *   g_logp = (s1 <= s2) ? -adv ratio : 0                          a tie takes the unclipped branch
+ *   without old_values: vl = (v - ret)^2 / 2; g_v = v - ret
+ *   with old_values:    vc = old_v + min(max(v - old_v, -vf_clip), vf_clip); u = (v - ret)^2; c = (vc - ret)^2
+ *                       vl = max(u, c) / 2; g_v = (u >= c) ? v - ret : (|v - old_v| <= vf_clip ? vc - ret : 0)
+ *   loss = (mean(pl) + vf_coef mean(vl)) - ent_coef mean(H), every mean over the `rows` rows of the call
+ *   k = scale / rows (scale NULL: 1)
+ *   dlogits[r][3h+c] = (float)(k (g_logp (1[c = a_h] - p_hc) + ent_coef (p_hc (lp_hc + H_h))))
+ *   dvalues[r]       = (float)(k (vf_coef g_v))
+ * stats is a device double[8]: loss, policy_loss = mean(pl), value_loss = mean(vl), entropy = mean(H),
+ * approx_kl = mean((ratio - 1) - log ratio), clip_frac = the share of rows with |ratio - 1| > clip,
+ * ratio_max, rows. The sums are float64 and use no atomics: lane-local, then a wave's lanes in lane
+ * order, then the partials in a fixed order; the association is a function of `rows` alone, so the same
+ * arguments give the same bits on every call and stream. Non-finite inputs give unspecified results.
+ *
+ * macm_policy_logp: logp [rows] (and entropy [rows] unless NULL) from logits [rows, 9] and actions
+ * uint8 [rows, 3]: the old_logp of a trajectory from the logits macm_world_rollout_policy stored.
+ * MACM_E_INVALID: logits, actions or logp NULL, rows < 0, a misaligned pointer. rows = 0 writes nothing.
+ *
+ * macm_ppo_loss: either half may be left out: logits NULL (then actions, old_logp and adv are not read
+ * and the policy statistics are 0) or values NULL (likewise ret, old_values and value_loss). old_values
+ * NULL selects the unclipped value loss. scale is a DEVICE pointer to one float (an autograd's incoming
+ * gradient, handed over without a synchronise) or NULL. dlogits, dvalues and stats may each be NULL:
+ * that output is not written. rows = 0 zeros stats and touches nothing else. No output may alias an input.
+ *
+ * macm_ppo_grad: the loss inside the gradient launch, one launch per net that is given (either may be
+ * NULL) plus the reductions: the forward is macm_policy_mlp's / macm_value_mlp's through the last
+ * layer, the row's dL/dout is the definition above on those outputs with scale = 1, and everything
+ * behind it is macm_policy_grad's / macm_value_grad's, so grad_policy and grad_value have the bits of
+ * macm_policy_flock (logits) / macm_value_flock -> macm_ppo_loss -> macm_policy_grad / macm_value_grad
+ * while neither the logits nor dL/dlogits exist in memory. Both are overwritten, not accumulated;
+ * rows = 0 writes zeros. stats (or NULL) is as above, with the half of a net that is not given 0; its
+ * sums are associated per wave of 64 rows, so they may differ from macm_ppo_loss's in the last bits.
+ *
+ * The caller owns the workspace as for macm_policy_grad: device memory, 16-byte aligned, at least
+ * macm_ppo_workspace(rows) bytes (the gradient partials and behind them the stat partials), a
+ * nondecreasing function of rows only; its contents after a call are unspecified and two calls in
+ * flight need one each. Everything is ordered on `stream`. Additive: MACM_ABI_VERSION stays 9.
+ * MACM_E_INVALID, with a message and nothing launched: cfg NULL, clip <= 0, a negative vf_coef or
+ * ent_coef, vf_clip <= 0 where old_values is given, reserved != 0, rows < 0, logits and values both
+ * NULL (macm_ppo_grad: both nets NULL, a net outside the supported shapes, nets of different in_dim,
+ * obs NULL), actions, old_logp or adv NULL where logits (the policy) is given, ret NULL where values
+ * (the critic) is given, a gradient output NULL for a net that is given, dlogits (dvalues) without
+ * logits (values), a misaligned pointer (float32 arrays 4 bytes, stats 8, workspace 16), workspace
+ * NULL or workspace_bytes too small while rows > 0; macm_ppo_workspace: rows < 0 or bytes NULL.
+ */
+typedef struct macm_ppo_config {
+  float clip, vf_coef, ent_coef, vf_clip;
+  int32_t reserved[4];
+} macm_ppo_config;
+
+int macm_policy_logp(const float* logits /* [rows, 9] */, const uint8_t* actions /* [rows, 3] */, int64_t rows,
+                     float* logp /* [rows] */, float* entropy /* [rows] or NULL */, void* stream);
+int macm_ppo_workspace(int64_t rows, int64_t* bytes);
+int macm_ppo_loss(const macm_ppo_config* cfg, int64_t rows, const float* logits, const uint8_t* actions,
+                  const float* old_logp, const float* adv, const float* values, const float* ret,
+                  const float* old_values, const float* scale, float* dlogits, float* dvalues, double* stats,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+int macm_ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c, const void* obs,
+                  int32_t obs_f64, int64_t rows, const uint8_t* actions, const float* old_logp, const float* adv,
+                  const float* ret, const float* old_values, float* grad_policy, float* grad_value, double* stats,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Observation of the current state without stepping (Flock.get_obs, mvmnt.py:181-222). */
 int macm_world_observe(macm_world* w, const macm_outputs* out, void* stream);
 
