@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from action_gen import random_flock_actions
 from guard_bands import FILL, GuardedOutputs
 from parity import assert_state_equal
 from test_gpu_tdm import assert_tdm_state_equal
@@ -52,9 +53,7 @@ def flock_worlds(E, N, seed, obs_f64=False, debug=0, **kw):
 
 
 def flock_actions(K, E, N, seed):
-    g = torch.Generator(device=DEV)
-    g.manual_seed(seed)
-    return torch.randint(0, 3, (K, E, N, 3), dtype=torch.uint8, device=DEV, generator=g)
+    return random_flock_actions((K, E, N), seed)
 
 
 def flock_twin_outputs(t):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from action_gen import random_flock_actions
 from parity import assert_state_equal
 from test_gpu_parity import make_pair
 
@@ -19,11 +20,7 @@ from gym_macm.vec import FlockVec  # noqa: E402
 
 
 def flock_actions(K, E, N, seed, continuous=False):
-    g = torch.Generator(device="cuda:0")
-    g.manual_seed(seed)
-    if continuous:
-        return torch.rand((K, E, N, 2), device="cuda:0", generator=g) * 2 - 1
-    return torch.randint(0, 3, (K, E, N, 3), dtype=torch.uint8, device="cuda:0", generator=g)
+    return random_flock_actions((K, E, N), seed, continuous)
 
 
 def outputs(w):

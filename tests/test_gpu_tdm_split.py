@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+from action_gen import random_tdm_actions
+
 pytestmark = pytest.mark.gpu
 
 from gym_macm import _abi  # noqa: E402
@@ -22,11 +24,7 @@ from gym_macm.tdm_world import TdmWorld, tdm_config  # noqa: E402
 
 
 def actions(K, E, N, seed, p_attack=0.5):
-    g = torch.Generator(device="cuda:0")
-    g.manual_seed(seed)
-    a = torch.randint(0, 3, (K, E, N, 4), dtype=torch.uint8, device="cuda:0", generator=g)
-    a[..., 3] = (torch.rand((K, E, N), device="cuda:0", generator=g) < p_attack).to(torch.uint8)
-    return a
+    return random_tdm_actions((K, E, N), seed, p_attack)
 
 
 def same_outputs(a, b, ctx):
