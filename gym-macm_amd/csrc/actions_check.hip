@@ -11,6 +11,7 @@
 // One thread per agent row; the lowest failing flat row index is kept (atomicMin), so the host
 // can name the first offending (env, agent). Not on the hot path: it runs only when enabled.
 #include "flock_common.hpp"
+#include "launch.hpp"
 
 namespace macm {
 

@@ -3,6 +3,7 @@
 // closed-loop rollouts never leave HBM.
 // The decisions themselves are in bots.hpp (shared with the closed-loop rollout).
 #include "bots.hpp"
+#include "launch.hpp"
 
 namespace macm {
 

@@ -1,0 +1,237 @@
+// capi_learn.hip — the stateless part of the C-ABI of libmacm_hip.so (declared in include/macm.h): the
+// version and last-error calls, the one-shot policy, value and GAE kernels, the gradients, the PPO loss
+// and the scripted actors. No world, no torch types, no exceptions across the ABI.
+#include "capi_common.hpp"
+
+static thread_local std::string g_last_error;
+
+int fail(int code, const std::string& msg) {
+  g_last_error = msg;
+  return code;
+}
+
+extern "C" {
+
+const char* macm_version(void) {
+  return "macm-hip 0.6.0 (gfx950; Flock: wave-per-env kernel N<=64, workgroup-per-env kernels N<=1024, "
+         "spill step for dense envs and N<=4096; TDM: wave-per-env kernel N<=64, workgroup step N<=4096)";
+}
+int macm_abi_version(void) { return MACM_ABI_VERSION; }
+const char* macm_last_error(void) { return g_last_error.c_str(); }
+
+int macm_policy_flock(const macm_policy_mlp* p, const void* obs, int32_t obs_f64, int64_t rows, const float* noise,
+                      uint8_t* actions, float* logits, void* stream) {
+  if (!p) return fail(MACM_E_INVALID, "policy is NULL");
+  if (const int rc = mlp_check("policy", p)) return rc;
+  if (!obs || !actions) return fail(MACM_E_INVALID, "obs/actions is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "rows must be >= 0");
+  const PolicyArgs M{p->params, noise, logits, p->hidden, p->n_hidden};
+  HIP_TRY(launch_policy_flock(M, obs, obs_f64 != 0, p->in_dim, rows, actions, (hipStream_t)stream));
+  return MACM_OK;
+}
+
+int macm_value_flock(const macm_value_mlp* c, const void* obs, int32_t obs_f64, int64_t rows, float* values,
+                     void* stream) {
+  if (!c) return fail(MACM_E_INVALID, "critic is NULL");
+  if (const int rc = mlp_check("critic", c)) return rc;
+  if (!obs || !values) return fail(MACM_E_INVALID, "obs/values is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "rows must be >= 0");
+  const ValueArgs V{c->params, nullptr, nullptr, c->hidden, c->n_hidden};
+  HIP_TRY(launch_value_flock(V, obs, obs_f64 != 0, c->in_dim, rows, values, (hipStream_t)stream));
+  return MACM_OK;
+}
+
+int macm_gae(const float* reward, const float* values, const float* boot, const uint8_t* done, int32_t n_steps,
+             int32_t n_envs, int32_t n_agents, float gamma, float lambda, float* adv, float* ret, void* stream) {
+  if (!reward || !values || !boot || !done || !adv || !ret)
+    return fail(MACM_E_INVALID, "gae: reward/values/boot/done/adv/ret is NULL");
+  if (n_steps < 0 || n_envs < 0 || n_agents < 0) return fail(MACM_E_INVALID, "gae: n_steps, n_envs, n_agents must be >= 0");
+  const GaeShape g{n_steps, n_envs, n_agents, gamma, lambda};
+  HIP_TRY(launch_gae(reward, values, boot, done, g, adv, ret, (hipStream_t)stream));
+  return MACM_OK;
+}
+
+// The workspace of macm_policy_grad / macm_value_grad: one partial of the largest net per wave
+static int64_t mlp_grad_workspace_bytes(int64_t rows) {
+  return (int64_t)mlp_grad_partials(rows) * kGradMaxParams * (int64_t)sizeof(float);
+}
+
+int macm_mlp_grad_workspace(int64_t rows, int64_t* bytes) {
+  if (!bytes) return fail(MACM_E_INVALID, "grad: bytes is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "grad: rows must be >= 0");
+  *bytes = mlp_grad_workspace_bytes(rows);
+  return MACM_OK;
+}
+
+// A checked policy (n_out = kPolicyLogits) or critic (1) as the gradient launches take it
+extern "C++" template <typename M>
+static MlpNet net_of(const M* m, int n_out) {
+  return MlpNet{m->params, m->in_dim, m->hidden, m->n_hidden, n_out};
+}
+
+// What the two gradient calls share behind their struct checks
+static int mlp_grad(const MlpNet& net, const void* obs, int32_t obs_f64, int64_t rows, const float* dout, float* grad,
+                    void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!obs || !dout || !grad) return fail(MACM_E_INVALID, "grad: obs/dout/grad is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "grad: rows must be >= 0");
+  if (rows > 0 && !workspace) return fail(MACM_E_INVALID, "grad: workspace is NULL");
+  if (rows > 0 && (reinterpret_cast<uintptr_t>(workspace) & 15))
+    return fail(MACM_E_INVALID, "grad: workspace must be 16-byte aligned");
+  if (rows > 0 && workspace_bytes < mlp_grad_workspace_bytes(rows))
+    return fail(MACM_E_INVALID, "grad: workspace_bytes " + std::to_string(workspace_bytes) + " is below the " +
+                                    std::to_string(mlp_grad_workspace_bytes(rows)) + " of macm_mlp_grad_workspace");
+  HIP_TRY(launch_mlp_grad(net, obs, obs_f64 != 0, rows, dout, grad, (float*)workspace, (hipStream_t)stream));
+  return MACM_OK;
+}
+
+int macm_policy_grad(const macm_policy_mlp* p, const void* obs, int32_t obs_f64, int64_t rows, const float* dlogits,
+                     float* grad, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!p) return fail(MACM_E_INVALID, "policy is NULL");
+  if (const int rc = mlp_check("policy", p)) return rc;
+  return mlp_grad(net_of(p, kPolicyLogits), obs, obs_f64, rows, dlogits, grad, workspace, workspace_bytes, stream);
+}
+
+int macm_value_grad(const macm_value_mlp* c, const void* obs, int32_t obs_f64, int64_t rows, const float* dvalues,
+                    float* grad, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!c) return fail(MACM_E_INVALID, "critic is NULL");
+  if (const int rc = mlp_check("critic", c)) return rc;
+  return mlp_grad(net_of(c, 1), obs, obs_f64, rows, dvalues, grad, workspace, workspace_bytes, stream);
+}
+
+// ---- the PPO loss (ppo_row.hpp): one-shot kernels and loss-to-gradient launches ------------------------
+static bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+static int64_t align16(int64_t n) { return (n + 15) & ~(int64_t)15; }
+
+// The workspace of macm_ppo_loss / macm_ppo_grad: the gradient partials, and behind them one stat partial
+// per wave (macm_ppo_loss has at most as many blocks as macm_ppo_grad has waves)
+static int64_t ppo_stat_offset(int64_t rows) { return align16(mlp_grad_workspace_bytes(rows)); }
+static int64_t ppo_workspace_bytes(int64_t rows) {
+  return ppo_stat_offset(rows) + (int64_t)mlp_grad_partials(rows) * kPpoStatSlots * (int64_t)sizeof(double);
+}
+
+int macm_ppo_workspace(int64_t rows, int64_t* bytes) {
+  if (!bytes) return fail(MACM_E_INVALID, "ppo: bytes is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "ppo: rows must be >= 0");
+  *bytes = ppo_workspace_bytes(rows);
+  return MACM_OK;
+}
+
+int macm_policy_logp(const float* logits, const uint8_t* actions, int64_t rows, float* logp, float* entropy,
+                     void* stream) {
+  if (!logits || !actions || !logp) return fail(MACM_E_INVALID, "logp: logits/actions/logp is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "logp: rows must be >= 0");
+  if (misaligned(logits, 4) || misaligned(logp, 4) || misaligned(entropy, 4))
+    return fail(MACM_E_INVALID, "logp: logits, logp and entropy must be 4-byte aligned");
+  HIP_TRY(launch_policy_logp(logits, actions, rows, logp, entropy, (hipStream_t)stream));
+  return MACM_OK;
+}
+
+// What macm_ppo_loss and macm_ppo_grad check alike: the config, rows and the workspace
+static int ppo_check(const macm_ppo_config* cfg, int64_t rows, bool clipped_value, const double* stats,
+                     const void* workspace, int64_t workspace_bytes) {
+  if (!cfg) return fail(MACM_E_INVALID, "ppo: cfg is NULL");
+  if (!(cfg->clip > 0.0f)) return fail(MACM_E_INVALID, "ppo: clip must be > 0");
+  if (!(cfg->vf_coef >= 0.0f) || !(cfg->ent_coef >= 0.0f))
+    return fail(MACM_E_INVALID, "ppo: vf_coef and ent_coef must be >= 0");
+  if (clipped_value && !(cfg->vf_clip > 0.0f))
+    return fail(MACM_E_INVALID, "ppo: vf_clip must be > 0 where old_values is given");
+  for (int i = 0; i < 4; ++i)
+    if (cfg->reserved[i] != 0) return fail(MACM_E_INVALID, "ppo: reserved must be 0");
+  if (rows < 0) return fail(MACM_E_INVALID, "ppo: rows must be >= 0");
+  if (misaligned(stats, 8)) return fail(MACM_E_INVALID, "ppo: stats must be 8-byte aligned");
+  if (rows > 0 && !workspace) return fail(MACM_E_INVALID, "ppo: workspace is NULL");
+  if (rows > 0 && misaligned(workspace, 16)) return fail(MACM_E_INVALID, "ppo: workspace must be 16-byte aligned");
+  if (rows > 0 && workspace_bytes < ppo_workspace_bytes(rows))
+    return fail(MACM_E_INVALID, "ppo: workspace_bytes " + std::to_string(workspace_bytes) + " is below the " +
+                                    std::to_string(ppo_workspace_bytes(rows)) + " of macm_ppo_workspace");
+  return MACM_OK;
+}
+
+int macm_ppo_loss(const macm_ppo_config* cfg, int64_t rows, const float* logits, const uint8_t* actions,
+                  const float* old_logp, const float* adv, const float* values, const float* ret,
+                  const float* old_values, const float* scale, float* dlogits, float* dvalues, double* stats,
+                  void* workspace, int64_t workspace_bytes, void* stream) {
+  if (const int rc = ppo_check(cfg, rows, old_values != nullptr, stats, workspace, workspace_bytes)) return rc;
+  if (!logits && !values) return fail(MACM_E_INVALID, "ppo: logits and values are both NULL");
+  if (logits && (!actions || !old_logp || !adv))
+    return fail(MACM_E_INVALID, "ppo: actions/old_logp/adv is NULL where logits is given");
+  if (values && !ret) return fail(MACM_E_INVALID, "ppo: ret is NULL where values is given");
+  if (dlogits && !logits) return fail(MACM_E_INVALID, "ppo: dlogits is wanted but logits is NULL");
+  if (dvalues && !values) return fail(MACM_E_INVALID, "ppo: dvalues is wanted but values is NULL");
+  for (const void* p : {(const void*)logits, (const void*)old_logp, (const void*)adv, (const void*)values,
+                        (const void*)ret, (const void*)old_values, (const void*)scale, (const void*)dlogits,
+                        (const void*)dvalues})
+    if (misaligned(p, 4)) return fail(MACM_E_INVALID, "ppo: the float32 arrays must be 4-byte aligned");
+  const hipStream_t s = (hipStream_t)stream;
+  if (rows == 0) {
+    if (stats) HIP_TRY(hipMemsetAsync(stats, 0, 8 * sizeof(double), s));
+    return MACM_OK;
+  }
+  const PpoCfg c{cfg->clip, cfg->vf_coef, cfg->ent_coef, cfg->vf_clip};
+  double* const part = stats ? reinterpret_cast<double*>((char*)workspace + ppo_stat_offset(rows)) : nullptr;
+  const PpoLossArgs A{logits, actions, old_logp, adv, values, ret, old_values, scale, dlogits, dvalues, part, c};
+  HIP_TRY(launch_ppo_loss(A, rows, s));
+  if (stats)
+    HIP_TRY(launch_ppo_stats(part, (int)ppo_loss_partials(rows), rows, c, logits != nullptr, values != nullptr, stats, s));
+  return MACM_OK;
+}
+
+int macm_ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c, const void* obs,
+                  int32_t obs_f64, int64_t rows, const uint8_t* actions, const float* old_logp, const float* adv,
+                  const float* ret, const float* old_values, float* grad_policy, float* grad_value, double* stats,
+                  void* workspace, int64_t workspace_bytes, void* stream) {
+  if (const int rc = ppo_check(cfg, rows, c && old_values, stats, workspace, workspace_bytes)) return rc;
+  if (!p && !c) return fail(MACM_E_INVALID, "ppo: policy and critic are both NULL");
+  if (p) {
+    if (const int rc = mlp_check("policy", p)) return rc;
+    if (!actions || !old_logp || !adv || !grad_policy)
+      return fail(MACM_E_INVALID, "ppo: actions/old_logp/adv/grad_policy is NULL where the policy is given");
+  }
+  if (c) {
+    if (const int rc = mlp_check("critic", c)) return rc;
+    if (!ret || !grad_value) return fail(MACM_E_INVALID, "ppo: ret/grad_value is NULL where the critic is given");
+  }
+  if (p && c && p->in_dim != c->in_dim)
+    return fail(MACM_E_INVALID, "ppo: the policy's in_dim and the critic's differ (they read the same obs rows)");
+  if (!obs) return fail(MACM_E_INVALID, "ppo: obs is NULL");
+  for (const void* q : {(const void*)old_logp, (const void*)adv, (const void*)ret, (const void*)old_values,
+                        (const void*)grad_policy, (const void*)grad_value})
+    if (misaligned(q, 4)) return fail(MACM_E_INVALID, "ppo: the float32 arrays must be 4-byte aligned");
+  const hipStream_t s = (hipStream_t)stream;
+  if (rows == 0) {
+    if (p) HIP_TRY(hipMemsetAsync(grad_policy, 0, sizeof(float) * net_of(p, kPolicyLogits).n_params(), s));
+    if (c) HIP_TRY(hipMemsetAsync(grad_value, 0, sizeof(float) * net_of(c, 1).n_params(), s));
+    if (stats) HIP_TRY(hipMemsetAsync(stats, 0, 8 * sizeof(double), s));
+    return MACM_OK;
+  }
+  const PpoCfg k{cfg->clip, cfg->vf_coef, cfg->ent_coef, cfg->vf_clip};
+  double* const part = stats ? reinterpret_cast<double*>((char*)workspace + ppo_stat_offset(rows)) : nullptr;
+  const PpoGradArgs G{actions, old_logp, adv, ret, c ? old_values : nullptr, k, 1.0 / (double)rows, part};
+  if (p)
+    HIP_TRY(launch_mlp_ppo_grad(net_of(p, kPolicyLogits), obs, obs_f64 != 0, rows, G, grad_policy, (float*)workspace, s));
+  if (c)
+    HIP_TRY(launch_mlp_ppo_grad(net_of(c, 1), obs, obs_f64 != 0, rows, G, grad_value, (float*)workspace, s));
+  if (stats)
+    HIP_TRY(launch_ppo_stats(part, (int)mlp_grad_partials(rows), rows, k, p != nullptr, c != nullptr, stats, s));
+  return MACM_OK;
+}
+
+// ============================ scripted actors ===============================
+
+int macm_bots_flock(const void* obs, int32_t obs_f64, int32_t obs_dim, int64_t rows, uint8_t* actions,
+                    void* stream) {
+  if (!obs || !actions || rows < 0) return fail(MACM_E_INVALID, "obs/actions NULL or rows < 0");
+  if (obs_dim != 4 && obs_dim != 6) return fail(MACM_E_INVALID, "obs_dim must be 4 (polar) or 6 (cartesian)");
+  HIP_TRY(launch_bots_flock(obs, obs_f64 != 0, obs_dim, rows, actions, (hipStream_t)stream));
+  return MACM_OK;
+}
+
+int macm_bots_combat(const void* obs, const uint8_t* mask, int32_t obs_f64, int32_t n_agents, int64_t rows,
+                     uint8_t* actions, void* stream) {
+  if (!obs || !mask || !actions || rows < 0) return fail(MACM_E_INVALID, "obs/mask/actions NULL or rows < 0");
+  if (n_agents < 2) return fail(MACM_E_INVALID, "n_agents must be >= 2");
+  HIP_TRY(launch_bots_combat(obs, mask, obs_f64 != 0, n_agents, rows, actions, (hipStream_t)stream));
+  return MACM_OK;
+}
+
+}  // extern "C"

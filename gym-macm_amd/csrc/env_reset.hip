@@ -16,6 +16,7 @@
 // Every operation is integer or exactly rounded double arithmetic, so the poses
 // equal the host generator's bit for bit.
 #include "flock_common.hpp"
+#include "launch.hpp"
 
 namespace macm {
 
@@ -154,11 +155,11 @@ __global__ __launch_bounds__(256) void final_copy_kernel(const uint8_t* __restri
   }
 }
 
-hipError_t launch_final_copy(const uint8_t* mask, const FinalOut& F, const void* obs, const int32_t* nbr,
-                             const uint8_t* msk, const int32_t* step_count, unsigned long long obs_bytes, int n_nbr,
-                             int n_msk, int n_envs, hipStream_t s) {
-  hipLaunchKernelGGL(final_copy_kernel, dim3(n_envs), dim3(256), 0, s, mask, F, static_cast<const unsigned char*>(obs),
-                     nbr, msk, step_count, obs_bytes, n_nbr, n_msk);
+hipError_t launch_final_copy(const uint8_t* mask, const FinalOut& F, const FinalRows& rows,
+                             const int32_t* step_count, int n_envs, hipStream_t s) {
+  hipLaunchKernelGGL(final_copy_kernel, dim3(n_envs), dim3(256), 0, s, mask, F,
+                     static_cast<const unsigned char*>(rows.obs), rows.nbr, rows.msk, step_count, rows.obs_bytes,
+                     rows.n_nbr, rows.n_msk);
   return hipGetLastError();
 }
 

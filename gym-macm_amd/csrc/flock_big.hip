@@ -18,6 +18,7 @@
 
 #include "flock_common.hpp"
 #include "flock_spill.hpp"
+#include "launch.hpp"
 
 namespace macm {
 namespace big {
@@ -207,26 +208,19 @@ hipError_t big_configure(int N) {
   return e;
 }
 
-hipError_t launch_step_big(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
-                           bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s) {
+hipError_t launch_step_big(const StepParams& P, const WorldBuffers& B, int cur, const FlockIO& io, hipStream_t s) {
   const dim3 grid(P.n_envs), block(big::kBS);
   const int lds = big_step_lds(P.n_agents);
   const bool four = P.n_agents > 2 * big::kBS;
-  if (obs_f64) {
+  with_obs_type(io.obs_f64, [&](auto ot) {
+    using OT = decltype(ot);
     if (four)
-      hipLaunchKernelGGL((flock_step_big<double, 4>), grid, block, lds, s, P, B, cur, actions, (double*)obs, nbr, rew,
-                         coll, done);
+      hipLaunchKernelGGL((flock_step_big<OT, 4>), grid, block, lds, s, P, B, cur, io.actions, (OT*)io.obs, io.nbr, io.rew,
+                         io.coll, io.done);
     else
-      hipLaunchKernelGGL((flock_step_big<double, 2>), grid, block, lds, s, P, B, cur, actions, (double*)obs, nbr, rew,
-                         coll, done);
-  } else {
-    if (four)
-      hipLaunchKernelGGL((flock_step_big<float, 4>), grid, block, lds, s, P, B, cur, actions, (float*)obs, nbr, rew,
-                         coll, done);
-    else
-      hipLaunchKernelGGL((flock_step_big<float, 2>), grid, block, lds, s, P, B, cur, actions, (float*)obs, nbr, rew,
-                         coll, done);
-  }
+      hipLaunchKernelGGL((flock_step_big<OT, 2>), grid, block, lds, s, P, B, cur, io.actions, (OT*)io.obs, io.nbr, io.rew,
+                         io.coll, io.done);
+  });
   return hipGetLastError();
 }
 
@@ -234,10 +228,9 @@ hipError_t launch_init_big(const StepParams& P, const WorldBuffers& B, int cur, 
                            const uint8_t* mask, hipStream_t s) {
   const dim3 grid(P.n_envs), block(big::kBS);
   const int lds = big_init_lds(P.n_agents);
-  if (obs_f64)
-    hipLaunchKernelGGL(flock_init_big<double>, grid, block, lds, s, P, B, cur, (double*)obs, nbr, mask);
-  else
-    hipLaunchKernelGGL(flock_init_big<float>, grid, block, lds, s, P, B, cur, (float*)obs, nbr, mask);
+  with_obs_type(obs_f64, [&](auto ot) {
+    hipLaunchKernelGGL(flock_init_big<decltype(ot)>, grid, block, lds, s, P, B, cur, (decltype(ot)*)obs, nbr, mask);
+  });
   return hipGetLastError();
 }
 
@@ -245,10 +238,9 @@ hipError_t launch_observe_big(const StepParams& P, const WorldBuffers& B, void* 
                               hipStream_t s) {
   const dim3 grid(P.n_envs), block(big::kBS);
   const int lds = 8 * P.n_agents;
-  if (obs_f64)
-    hipLaunchKernelGGL(flock_observe_big<double>, grid, block, lds, s, P, B, (double*)obs, nbr);
-  else
-    hipLaunchKernelGGL(flock_observe_big<float>, grid, block, lds, s, P, B, (float*)obs, nbr);
+  with_obs_type(obs_f64, [&](auto ot) {
+    hipLaunchKernelGGL(flock_observe_big<decltype(ot)>, grid, block, lds, s, P, B, (decltype(ot)*)obs, nbr);
+  });
   return hipGetLastError();
 }
 

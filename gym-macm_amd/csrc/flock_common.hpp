@@ -171,7 +171,7 @@ __device__ __forceinline__ int ld_wt(const int* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Host side of a world's handoff (macm_capi.hip): kernel C's stream, the join event, the device
+// Host side of a world's handoff (capi_world.hip): kernel C's stream, the join event, the device
 // words of Handoff, the last step's tag and the b_started count the next step waits for.
 struct HandoffStream {
   hipStream_t stream;

@@ -49,10 +49,13 @@
 //     solver is a signed zero; dropping them can change only the sign of a zero
 //     velocity/impulse component, never a nonzero value or any position.
 //   * circles sit at the body origin, so b2Mul(xf, m_p) == position exactly.
+#include <type_traits>
+
 #include "bots.hpp"
 #include "policy_mlp.hpp"
 #include "flock_common.hpp"
 #include "flock_spill.hpp"
+#include "launch.hpp"
 #include "tdm_obs.hpp"
 
 // (a translation unit that defines MACM_KS_SWITCH, macm_math.h, pins in its Flock steps; TDM never)
@@ -879,7 +882,7 @@ __device__ __forceinline__ int write_new_pairs(int lane, unsigned long long newm
 // in step-major order from a shared counter, each once its env's ready word covers the step, until
 // all K x E rows are taken. Extra blocks (blockIdx.x >= E) only observe. The observations of the envs
 // that end first run beside the heaviest envs' physics. A wait that does not end within ~1 s (never
-// expected: every env's wave is resident, macm_capi checks the occupancy, and never waits) reports
+// expected: every env's wave is resident, capi_tdm.hip checks the occupancy, and never waits) reports
 // MACM_ST_HANDOFF and ends the worker. Each row is the fused form's observation of the same snapshot
 // values (tdm_obs_rowblocks / tdm_obs_pairs), bit for bit.
 struct TailObs {
@@ -2698,6 +2701,23 @@ __device__ __forceinline__ void tdm_init_env(const StepParams& P, const WorldBuf
   }
 }
 
+// The instantiation of the wave kernels a world runs, from its mode, agent count and obs type:
+// f(NCAP, OT, SCAL) as f(std::integral_constant<int, 32 | 64>, float | double, std::bool_constant<SCAL>).
+// SCAL (the scalar sweep): Flock, float obs, more than 32 agents, n_envs >= kScalarSweepMinEnvs.
+template <int MODE, typename F>
+static void with_instance(const StepParams& P, bool obs_f64, F&& f) {
+  using N32 = std::integral_constant<int, 32>;
+  using N64 = std::integral_constant<int, 64>;
+  constexpr std::false_type no{};
+  const bool small = P.n_agents <= 32;  // (the calls below in the order the kernels have always been emitted in)
+  if (obs_f64) return small ? f(N32{}, double{}, no) : f(N64{}, double{}, no);
+  if (small) return f(N32{}, float{}, no);
+  if constexpr (MODE == kFlock) {
+    if (P.n_envs >= kScalarSweepMinEnvs) return f(N64{}, float{}, std::true_type{});
+  }
+  f(N64{}, float{}, no);
+}
+
 #ifdef MACM_ROLLOUT_TU
 
 // nsteps consecutive steps of env blockIdx.x in one launch (macm_world_rollout): actions of step k
@@ -2737,9 +2757,10 @@ struct RolloutArgs {  // the kernel's only argument (kernarg offset 0)
   // A balanced launch steps envs order[sched_off + blockIdx.x]; sched_off is 0 since the solo split
   // was removed (round 6), and kept so that the kernel's argument layout (and with it its register
   // allocation) stays the measured one: without it the driver window ran 1.1% slower, with it 0.3%
-  // (in noise) against the library before the removal (profiles/r06/abtests/cleanup/).
+  // (in noise) against the library before the removal (profiles/r06/abtests/cleanup/). The fields
+  // after it are the tail observation's: tail_ctl, tail_tag, tail_k0.
   int sched_off;
-  // the tail observation (TailObs; TDM trajectory rollouts, macm_capi tdm_tail_obs): its counters and
+  // the tail observation (TailObs; TDM trajectory rollouts, capi_tdm.hip tdm_tail_obs): its counters and
   // ready words, and this launch's tag (0: off; blocks beyond n_envs then do not exist)
   unsigned long long* tail_ctl;
   unsigned int tail_tag;
@@ -2844,7 +2865,65 @@ __device__ __forceinline__ T* traj_row(T* p, size_t k, size_t per_step) {
 constexpr int kRollBalanceMinSteps = 32;
 constexpr int kSchedMaxSize = 4095;
 
-#ifdef MACM_AUTORESET_TU  // flock_rollout_ar_w64.hip: the rollout kernels of worlds with autoreset on
+// ---- host side of the rollout launches, shared with rollout_autoreset.inc ----
+// The rollout kernels' argument without the fields a tagged observation type adds, and without Flock's
+// own outputs (NULL: TDM has none). Every field named.
+template <typename OT>
+static RolloutArgs<OT> roll_args(const StepParams& P, const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB,
+                                 int cur, const StepIO& io, const RollShape& sh, const TailLaunch& tail) {
+  RolloutArgs<OT> A{};
+  A.P = P;
+  A.B = B;
+  A.TP = TP;
+  A.TB = TB;
+  A.actions = io.actions;
+  A.obs = (OT*)io.obs;
+  A.done_out = io.done;
+  A.astride = sh.astride;
+  A.cur = cur;
+  A.nsteps = sh.nsteps;
+  // astride == 0: closed loop, `actions` is the actor's action buffer (macm_world_rollout_bots)
+  A.policy_act = sh.astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(io.actions)) : nullptr;
+  A.traj = sh.traj;
+  A.sched_off = 0;
+  A.tail_ctl = tail.ctl;
+  A.tail_tag = tail.tag;
+  A.tail_k0 = tail.tag ? tail.k0 : 0;
+  return A;
+}
+
+template <typename T>
+struct TypeTag {
+  using type = T;
+};
+
+// The variant of a rollout kernel a launch takes, for env_rollout_w64 and env_rollout_ar_w64 alike:
+// go(TypeTag<OTA>, carry, fill) with OTA = OT or its ObsEv / ObsPol / ObsPolV tag, carry = CARRY as a
+// bool_constant and fill(R) setting the fields the tagged argument adds. Flock: the carried step where
+// the actions are given (closed = false), else the policy with or without the critic, else the bot;
+// TDM: the kernel that records the events where hit_out is set. `cur` takes the debug bits.
+template <int MODE, int NCAP, typename OT, typename Go>
+static void roll_variant(int& cur, bool closed, const FlockRollExtras& x, int32_t* hit_out, Go&& go) {
+  const auto none = [](auto&) {};
+  if constexpr (MODE == kFlock) {
+    if (NCAP == 64 && (x.debug & 2)) cur |= kRollNearPlainBit;
+    if (!closed) {
+      if (x.debug & 1) cur |= kRollReloadBit;
+      return go(TypeTag<OT>{}, std::true_type{}, none);
+    }
+    if (x.policy && x.critic)
+      return go(TypeTag<ObsPolV<OT>>{}, std::false_type{}, [&](auto& R) {
+        R.pol = *x.policy;
+        R.val = *x.critic;
+      });
+    if (x.policy) return go(TypeTag<ObsPol<OT>>{}, std::false_type{}, [&](auto& R) { R.pol = *x.policy; });
+  } else if (hit_out) {
+    return go(TypeTag<ObsEv<OT>>{}, std::false_type{}, [&](auto& R) { R.hit_out = hit_out; });
+  }
+  go(TypeTag<OT>{}, std::false_type{}, none);
+}
+
+#ifdef MACM_AUTORESET_TU // flock_rollout_ar_w64.hip: the rollout kernels of worlds with autoreset on
 #include "rollout_autoreset.inc"
 #else
 // order[0..E): the envs by descending contact-list size (ccount, clamped to C); one workgroup.
@@ -3019,15 +3098,15 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
 // Resident blocks of the TDM rollout kernel on this device (the tail observation needs every block
 // of a launch resident at once: a worker waits for envs whose waves must be running)
 int tdm_rollout_resident_blocks(int n_agents, bool obs_f64) {
-  const void* k = n_agents <= 32 ? (obs_f64 ? (const void*)env_rollout_w64<kTdm, 32, double>
-                                            : (const void*)env_rollout_w64<kTdm, 32, float>)
-                                 : (obs_f64 ? (const void*)env_rollout_w64<kTdm, 64, double>
-                                            : (const void*)env_rollout_w64<kTdm, 64, float>);
-  // the kernel of worlds with events registered: the same LDS and register budget, asked all the same
-  const void* kev = n_agents <= 32 ? (obs_f64 ? (const void*)env_rollout_w64<kTdm, 32, ObsEv<double>>
-                                              : (const void*)env_rollout_w64<kTdm, 32, ObsEv<float>>)
-                                   : (obs_f64 ? (const void*)env_rollout_w64<kTdm, 64, ObsEv<double>>
-                                              : (const void*)env_rollout_w64<kTdm, 64, ObsEv<float>>);
+  StepParams P{};
+  P.n_agents = n_agents;
+  // k: the rollout kernel; kev: that of worlds with events registered (the same LDS and register budget,
+  // asked all the same)
+  const void *k = nullptr, *kev = nullptr;
+  with_instance<kTdm>(P, obs_f64, [&](auto ncap, auto ot, auto) {
+    k = (const void*)env_rollout_w64<kTdm, decltype(ncap)::value, decltype(ot)>;
+    kev = (const void*)env_rollout_w64<kTdm, decltype(ncap)::value, ObsEv<decltype(ot)>>;
+  });
   int per = 0, per_ev = 0, dev = 0, cus = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, W, 0) != hipSuccess ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_ev, kev, W, 0) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
@@ -3038,63 +3117,28 @@ int tdm_rollout_resident_blocks(int n_agents, bool obs_f64) {
   return (per < per_ev ? per : per_ev) * cus;
 }
 
-template <int MODE, int NCAP, typename OT, bool SCAL = false>
-static void launch_roll(int nsteps, unsigned long long astride, int traj, hipStream_t s, const StepParams& P,
-                        const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur, const void* actions,
-                        void* obs, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done,
-                        unsigned long long* tail_ctl = nullptr, unsigned tail_tag = 0u, int tail_workers = 0,
-                        int tail_k0 = 0, int reload = 0,  // reload: bit 0 MACM_DEBUG_ROLLOUT_RELOAD, bit 1 _NEAR_PLAIN
-                        int32_t* hit_out = nullptr,       // TDM: non-NULL, the kernel that records the events
-                        const PolicyArgs* policy = nullptr,    // Flock closed loop: non-NULL, the MLP where the bot is
-                        const ValueArgs* critic = nullptr) {   // with policy: non-NULL, the critic beside it
-  // astride == 0: closed loop, `actions` is the bots' action buffer (macm_world_rollout_bots)
-  uint8_t* pol = astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(actions)) : nullptr;
-  const bool bal = B.sched && nsteps >= kRollBalanceMinSteps;
+template <int MODE, int NCAP, typename OT, bool SCAL>
+static void launch_roll(RolloutArgs<OT> A, int tail_workers, const FlockRollExtras& x, int32_t* hit_out, hipStream_t s) {
+  const StepParams& P = A.P;
+  const bool bal = A.B.sched && A.nsteps >= kRollBalanceMinSteps;
   if (bal) {
     // list sizes above kSchedMaxSize share the top bucket (any order among them is a valid order;
     // the histogram stays within 16 KB of LDS whatever max_contacts a world was given)
     const int CB = P.max_contacts < kSchedMaxSize ? P.max_contacts : kSchedMaxSize;
     hipLaunchKernelGGL(rollout_sched, dim3(1), dim3(1024), sizeof(uint32_t) * (CB + 1), s,
-                       reinterpret_cast<const uint32_t*>(B.ccount[cur]), B.sched, P.n_envs, CB, nullptr);
+                       reinterpret_cast<const uint32_t*>(A.B.ccount[A.cur]), A.B.sched, P.n_envs, CB, nullptr);
     if (hipPeekAtLastError() != hipSuccess) return;  // no rollout on a stale order (the caller reports it)
   }
-  RolloutArgs<OT> A{P, B, TP, TB, actions, (OT*)obs, nbr, rew, coll, done, astride, cur, nsteps, pol, traj, 0,
-                    tail_ctl, tail_tag, tail_tag ? tail_k0 : 0};
-  const int blocks = P.n_envs + (tail_tag ? tail_workers : 0);
-  if constexpr (MODE == kFlock) {
-    if (!pol) {  // actions given: the carried step
-      if (reload & 1) A.cur |= kRollReloadBit;
-      if (NCAP == 64 && (reload & 2)) A.cur |= kRollNearPlainBit;
-      hipLaunchKernelGGL((env_rollout_w64<MODE, NCAP, OT, SCAL, true>), dim3(blocks), dim3(W), 0, s, A);
-      return;
-    }
-    if (NCAP == 64 && (reload & 2)) A.cur |= kRollNearPlainBit;
-    if (policy && critic) {
-      RolloutArgs<ObsPolV<OT>> R;
-      static_cast<RolloutArgs<OT>&>(R) = A;
-      R.pol = *policy;
-      R.val = *critic;
-      hipLaunchKernelGGL((env_rollout_w64<kFlock, NCAP, ObsPolV<OT>, SCAL>), dim3(blocks), dim3(W), 0, s, R);
-      return;
-    }
-    if (policy) {
-      RolloutArgs<ObsPol<OT>> R;
-      static_cast<RolloutArgs<OT>&>(R) = A;
-      R.pol = *policy;
-      hipLaunchKernelGGL((env_rollout_w64<kFlock, NCAP, ObsPol<OT>, SCAL>), dim3(blocks), dim3(W), 0, s, R);
-      return;
-    }
-  } else if (hit_out) {
-    RolloutArgs<ObsEv<OT>> R;
+  const int blocks = P.n_envs + tail_workers;
+  roll_variant<MODE, NCAP, OT>(A.cur, A.policy_act != nullptr, x, hit_out, [&](auto tag, auto carry, auto&& fill) {
+    using OTA = typename decltype(tag)::type;
+    RolloutArgs<OTA> R;
     static_cast<RolloutArgs<OT>&>(R) = A;
-    R.hit_out = hit_out;
-    hipLaunchKernelGGL((env_rollout_w64<kTdm, NCAP, ObsEv<OT>>), dim3(blocks), dim3(W), 0, s, R);
-    return;
-  }
-  hipLaunchKernelGGL((env_rollout_w64<MODE, NCAP, OT, SCAL>), dim3(blocks), dim3(W), 0, s, A);
+    fill(R);
+    hipLaunchKernelGGL((env_rollout_w64<MODE, NCAP, OTA, SCAL, decltype(carry)::value>), dim3(blocks), dim3(W), 0, s, R);
+  });
 }
 
-// the same instantiation choice as launch_step_w64 / launch_tdm_step_w64
 // order[0..E): the envs by descending contact-list size (the workgroup step, kWgEnvOrder)
 hipError_t launch_env_order(const uint32_t* ccount, uint32_t* order, int E, int C, hipStream_t s, unsigned int* reset2) {
   const int CB = C < kSchedMaxSize ? C : kSchedMaxSize;
@@ -3102,55 +3146,29 @@ hipError_t launch_env_order(const uint32_t* ccount, uint32_t* order, int E, int 
   return hipGetLastError();
 }
 
-hipError_t launch_rollout_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
-                              bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
-                              int nsteps, unsigned long long astride, int traj, int reload, const PolicyArgs* policy,
-                              const ValueArgs* critic) {
+hipError_t launch_rollout_w64(const StepParams& P, const WorldBuffers& B, int cur, const FlockIO& io,
+                              const RollShape& sh, const FlockRollExtras& x, hipStream_t s) {
   const TdmParams TP{};
   const TdmBuffers TB{};
-  const bool small = P.n_agents <= 32;
-  if (obs_f64) {
-    if (small)
-      launch_roll<kFlock, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                     nullptr, 0u, 0, 0, reload, nullptr, policy, critic);
-    else
-      launch_roll<kFlock, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                     nullptr, 0u, 0, 0, reload, nullptr, policy, critic);
-  } else {
-    if (small)
-      launch_roll<kFlock, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                     nullptr, 0u, 0, 0, reload, nullptr, policy, critic);
-    else if (P.n_envs >= kScalarSweepMinEnvs)
-      launch_roll<kFlock, 64, float, true>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll,
-                                           done, nullptr, 0u, 0, 0, reload, nullptr, policy, critic);
-    else
-      launch_roll<kFlock, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                     nullptr, 0u, 0, 0, reload, nullptr, policy, critic);
-  }
+  with_instance<kFlock>(P, io.obs_f64, [&](auto ncap, auto ot, auto scal) {
+    using OT = decltype(ot);
+    RolloutArgs<OT> A = roll_args<OT>(P, B, TP, TB, cur, io, sh, TailLaunch{});
+    A.nbr_out = io.nbr;
+    A.rew_out = io.rew;
+    A.coll_out = io.coll;
+    launch_roll<kFlock, decltype(ncap)::value, OT, decltype(scal)::value>(A, 0, x, nullptr, s);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_tdm_rollout_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
-                                  const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
-                                  uint8_t* done, hipStream_t s, int nsteps, unsigned long long astride, int traj,
-                                  unsigned long long* tail_ctl, unsigned tail_tag, int tail_workers,
-                                  int tail_k0, int32_t* hit_out) {
-  const bool small = P.n_agents <= 32;
-  if (obs_f64) {
-    if (small)
-      launch_roll<kTdm, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                    nullptr, done, tail_ctl, tail_tag, tail_workers, tail_k0, 0, hit_out);
-    else
-      launch_roll<kTdm, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                    nullptr, done, tail_ctl, tail_tag, tail_workers, tail_k0, 0, hit_out);
-  } else {
-    if (small)
-      launch_roll<kTdm, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                   nullptr, done, tail_ctl, tail_tag, tail_workers, tail_k0, 0, hit_out);
-    else
-      launch_roll<kTdm, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                   nullptr, done, tail_ctl, tail_tag, tail_workers, tail_k0, 0, hit_out);
-  }
+                                  const TdmBuffers& TB, int cur, const TdmIO& io, const RollShape& sh,
+                                  const TailLaunch& tail, hipStream_t s) {
+  with_instance<kTdm>(P, io.obs_f64, [&](auto ncap, auto ot, auto scal) {
+    using OT = decltype(ot);
+    launch_roll<kTdm, decltype(ncap)::value, OT, decltype(scal)::value>(
+        roll_args<OT>(P, B, TP, TB, cur, io, sh, tail), tail.tag ? tail.workers : 0, FlockRollExtras{}, io.hit_out, s);
+  });
   return hipGetLastError();
 }
 
@@ -3305,71 +3323,31 @@ __global__ __launch_bounds__(W) void tdm_observe_w64(StepParams P, WorldBuffers 
                    s_p, s_a);
 }
 
-// ---- host-side launchers (C++ linkage, used by macm_capi.hip) -----------------
-template <int MODE, int NCAP, typename OT, bool SCAL = false>
-static void launch_w64(hipStream_t s, const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
-                       const TdmBuffers& TB, int cur, const void* actions, void* obs, int32_t* nbr, float* rew,
-                       uint8_t* coll, uint8_t* done) {
-  hipLaunchKernelGGL((env_step_w64<MODE, NCAP, OT, SCAL>), dim3(P.n_envs), dim3(W), 0, s, P, B, TP, TB, cur, actions,
-                     (OT*)obs, nbr, rew, coll, done);
-}
-
-hipError_t launch_step_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions,
-                           void* obs, bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done,
-                           hipStream_t s) {
+// ---- host-side launchers (declared in launch.hpp) -----------------
+hipError_t launch_step_w64(const StepParams& P, const WorldBuffers& B, int cur, const FlockIO& io, hipStream_t s) {
   const TdmParams TP{};
   const TdmBuffers TB{};
-  const bool small = P.n_agents <= 32;
-  if (obs_f64) {
-    if (small)
-      launch_w64<kFlock, 32, double>(s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done);
-    else
-      launch_w64<kFlock, 64, double>(s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done);
-  } else {
-    if (small)
-      launch_w64<kFlock, 32, float>(s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done);
-    else if (P.n_envs >= kScalarSweepMinEnvs)
-      launch_w64<kFlock, 64, float, true>(s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done);
-    else
-      launch_w64<kFlock, 64, float>(s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done);
-  }
+  with_instance<kFlock>(P, io.obs_f64, [&](auto ncap, auto ot, auto scal) {
+    using OT = decltype(ot);
+    hipLaunchKernelGGL((env_step_w64<kFlock, decltype(ncap)::value, OT, decltype(scal)::value>), dim3(P.n_envs), dim3(W),
+                       0, s, P, B, TP, TB, cur, io.actions, (OT*)io.obs, io.nbr, io.rew, io.coll, io.done);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_tdm_step_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
-                               const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
-                               uint8_t* done, hipStream_t s, int32_t* hit_out) {
-  const bool small = P.n_agents <= 32;
-  if (hit_out) {  // events registered: the kernel that records them
+                               const TdmBuffers& TB, int cur, const TdmIO& io, hipStream_t s) {
+  with_instance<kTdm>(P, io.obs_f64, [&](auto ncap, auto ot, auto) {
+    using OT = decltype(ot);
+    constexpr int NCAP = decltype(ncap)::value;
     const dim3 grid(P.n_envs), block(W);
-    if (obs_f64) {
-      if (small)
-        hipLaunchKernelGGL((env_step_ev_w64<32, double>), grid, block, 0, s, P, B, TP, TB, cur, actions, (double*)obs, done,
-                           hit_out);
-      else
-        hipLaunchKernelGGL((env_step_ev_w64<64, double>), grid, block, 0, s, P, B, TP, TB, cur, actions, (double*)obs, done,
-                           hit_out);
-    } else {
-      if (small)
-        hipLaunchKernelGGL((env_step_ev_w64<32, float>), grid, block, 0, s, P, B, TP, TB, cur, actions, (float*)obs, done,
-                           hit_out);
-      else
-        hipLaunchKernelGGL((env_step_ev_w64<64, float>), grid, block, 0, s, P, B, TP, TB, cur, actions, (float*)obs, done,
-                           hit_out);
-    }
-    return hipGetLastError();
-  }
-  if (obs_f64) {
-    if (small)
-      launch_w64<kTdm, 32, double>(s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr, nullptr, done);
+    if (io.hit_out)  // events registered: the kernel that records them
+      hipLaunchKernelGGL((env_step_ev_w64<NCAP, OT>), grid, block, 0, s, P, B, TP, TB, cur, io.actions, (OT*)io.obs,
+                         io.done, io.hit_out);
     else
-      launch_w64<kTdm, 64, double>(s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr, nullptr, done);
-  } else {
-    if (small)
-      launch_w64<kTdm, 32, float>(s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr, nullptr, done);
-    else
-      launch_w64<kTdm, 64, float>(s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr, nullptr, done);
-  }
+      hipLaunchKernelGGL((env_step_w64<kTdm, NCAP, OT>), grid, block, 0, s, P, B, TP, TB, cur, io.actions, (OT*)io.obs,
+                         (int32_t*)nullptr, (float*)nullptr, (uint8_t*)nullptr, io.done);
+  });
   return hipGetLastError();
 }
 
@@ -3377,40 +3355,36 @@ hipError_t launch_tdm_init_w64(const StepParams& P, const WorldBuffers& B, const
                                const TdmBuffers& TB, int cur, void* obs, bool obs_f64, const uint8_t* mask,
                                hipStream_t s) {
   dim3 grid(P.n_envs), block(W);
-  if (obs_f64)
-    hipLaunchKernelGGL(tdm_init_w64<double>, grid, block, 0, s, P, B, TP, TB, cur, (double*)obs, mask);
-  else
-    hipLaunchKernelGGL(tdm_init_w64<float>, grid, block, 0, s, P, B, TP, TB, cur, (float*)obs, mask);
+  with_obs_type(obs_f64, [&](auto ot) {
+    hipLaunchKernelGGL(tdm_init_w64<decltype(ot)>, grid, block, 0, s, P, B, TP, TB, cur, (decltype(ot)*)obs, mask);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_tdm_observe_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
                                   const TdmBuffers& TB, void* obs, bool obs_f64, hipStream_t s) {
   dim3 grid(P.n_envs), block(W);
-  if (obs_f64)
-    hipLaunchKernelGGL(tdm_observe_w64<double>, grid, block, 0, s, P, B, TP, TB, (double*)obs);
-  else
-    hipLaunchKernelGGL(tdm_observe_w64<float>, grid, block, 0, s, P, B, TP, TB, (float*)obs);
+  with_obs_type(obs_f64, [&](auto ot) {
+    hipLaunchKernelGGL(tdm_observe_w64<decltype(ot)>, grid, block, 0, s, P, B, TP, TB, (decltype(ot)*)obs);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_init_w64(const StepParams& P, const WorldBuffers& B, int cur, void* obs, bool obs_f64,
                            int32_t* nbr, const uint8_t* mask, hipStream_t s) {
   dim3 grid(P.n_envs), block(W);
-  if (obs_f64)
-    hipLaunchKernelGGL(flock_init_w64<double>, grid, block, 0, s, P, B, cur, (double*)obs, nbr, mask);
-  else
-    hipLaunchKernelGGL(flock_init_w64<float>, grid, block, 0, s, P, B, cur, (float*)obs, nbr, mask);
+  with_obs_type(obs_f64, [&](auto ot) {
+    hipLaunchKernelGGL(flock_init_w64<decltype(ot)>, grid, block, 0, s, P, B, cur, (decltype(ot)*)obs, nbr, mask);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_observe_w64(const StepParams& P, const WorldBuffers& B, void* obs, bool obs_f64, int32_t* nbr,
                               hipStream_t s) {
   dim3 grid(P.n_envs), block(W);
-  if (obs_f64)
-    hipLaunchKernelGGL(flock_observe_w64<double>, grid, block, 0, s, P, B, (double*)obs, nbr);
-  else
-    hipLaunchKernelGGL(flock_observe_w64<float>, grid, block, 0, s, P, B, (float*)obs, nbr);
+  with_obs_type(obs_f64, [&](auto ot) {
+    hipLaunchKernelGGL(flock_observe_w64<decltype(ot)>, grid, block, 0, s, P, B, (decltype(ot)*)obs, nbr);
+  });
   return hipGetLastError();
 }
 

@@ -25,10 +25,9 @@
 #include "flock_common.hpp"
 #include "flock_spill.hpp"
 #include "flock_grid.hpp"
+#include "launch.hpp"
 
 namespace macm {
-hipError_t launch_env_order(const uint32_t* ccount, uint32_t* order, int E, int C, hipStream_t s,
-                            unsigned int* reset2 = nullptr);
 
 // The step's env order (round 4): before each step the envs are ordered by contact-list size,
 // heaviest first (launch_env_order, one workgroup), and workgroup b of kernels A, DFS, B and C
@@ -2153,8 +2152,7 @@ hipError_t wg_configure(int N, int tcap) {
 // stream waits supported), kernel C runs on HS->stream as B's consumer (see Handoff): that stream
 // waits for every B wave to have started, C's blocks take the envs in B's finish order, and the
 // caller's stream waits for C at the end, so the call's results are complete on `s` as before.
-hipError_t launch_step_wg(const StepParams& P, const WorldBuffers& B, int cur, int tcap, const void* actions,
-                          void* obs, bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done,
+hipError_t launch_step_wg(const StepParams& P, const WorldBuffers& B, int cur, int tcap, const FlockIO& io,
                           hipStream_t s, HandoffStream* HS, uint8_t* bot_act) {
   dim3 grid(P.n_envs), block(wg_block(P.n_agents));
   Handoff H{nullptr, nullptr, nullptr, 0u};
@@ -2170,19 +2168,15 @@ hipError_t launch_step_wg(const StepParams& P, const WorldBuffers& B, int cur, i
   const int N = P.n_agents, la = wg_a_lds_bytes(N, tcap), lc = wg_layout_c(N).total;
   const int ld = wg::wg_layout_d(N, tcap).total;
   auto launch_c = [&](hipStream_t cs) {
-    if (obs_f64)
-      hipLaunchKernelGGL(flock_step_wg_c<double>, grid, block, lc, cs, P, B, cur, tcap, (double*)obs, nbr, rew, coll,
-                         done, H, bot_act);
-    else
-      hipLaunchKernelGGL(flock_step_wg_c<float>, grid, block, lc, cs, P, B, cur, tcap, (float*)obs, nbr, rew, coll,
-                         done, H, bot_act);
+    with_obs_type(io.obs_f64, [&](auto ot) {
+      hipLaunchKernelGGL(flock_step_wg_c<decltype(ot)>, grid, block, lc, cs, P, B, cur, tcap, (decltype(ot)*)io.obs, io.nbr,
+                         io.rew, io.coll, io.done, H, bot_act);
+    });
   };
-  if (obs_f64)
-    hipLaunchKernelGGL(flock_step_wg_a<double>, grid, block, la, s, P, B, cur, tcap, actions, (double*)obs, nbr, rew,
-                       coll, done);
-  else
-    hipLaunchKernelGGL(flock_step_wg_a<float>, grid, block, la, s, P, B, cur, tcap, actions, (float*)obs, nbr, rew,
-                       coll, done);
+  with_obs_type(io.obs_f64, [&](auto ot) {
+    hipLaunchKernelGGL(flock_step_wg_a<decltype(ot)>, grid, block, la, s, P, B, cur, tcap, io.actions, (decltype(ot)*)io.obs,
+                       io.nbr, io.rew, io.coll, io.done);
+  });
   // the watcher's clock starts only once kernel B's dependencies have finished: HS->stream
   // waits for this event, recorded on `s` right before B, so work queued on the caller's stream ahead
   // of the step (a policy update, another world's launches) cannot run the watcher out of time
@@ -2219,10 +2213,9 @@ hipError_t launch_init_wg(const StepParams& P, const WorldBuffers& B, int cur, v
                           hipStream_t s) {
   const int lds = wg_init_lds_bytes(P.n_agents);
   dim3 grid(P.n_envs), block(wg_block(P.n_agents));
-  if (obs_f64)
-    hipLaunchKernelGGL(flock_init_wg<double>, grid, block, lds, s, P, B, cur, (double*)obs, nbr, mask);
-  else
-    hipLaunchKernelGGL(flock_init_wg<float>, grid, block, lds, s, P, B, cur, (float*)obs, nbr, mask);
+  with_obs_type(obs_f64, [&](auto ot) {
+    hipLaunchKernelGGL(flock_init_wg<decltype(ot)>, grid, block, lds, s, P, B, cur, (decltype(ot)*)obs, nbr, mask);
+  });
   return hipGetLastError();
 }
 
@@ -2230,10 +2223,9 @@ hipError_t launch_observe_wg(const StepParams& P, const WorldBuffers& B, void* o
                              hipStream_t s) {
   const int lds = 8 * P.n_agents;
   dim3 grid(P.n_envs), block(wg_block(P.n_agents));
-  if (obs_f64)
-    hipLaunchKernelGGL(flock_observe_wg<double>, grid, block, lds, s, P, B, (double*)obs, nbr);
-  else
-    hipLaunchKernelGGL(flock_observe_wg<float>, grid, block, lds, s, P, B, (float*)obs, nbr);
+  with_obs_type(obs_f64, [&](auto ot) {
+    hipLaunchKernelGGL(flock_observe_wg<decltype(ot)>, grid, block, lds, s, P, B, (decltype(ot)*)obs, nbr);
+  });
   return hipGetLastError();
 }
 

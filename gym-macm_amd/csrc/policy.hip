@@ -91,14 +91,14 @@ __global__ __launch_bounds__(256) void gae_kernel(const float* __restrict__ rewa
   }
 }
 
-hipError_t launch_gae(const float* reward, const float* values, const float* boot, const uint8_t* done, int n_steps,
-                      long long n_envs, int n_agents, float gamma, float lambda, float* adv, float* ret, hipStream_t s) {
-  const long long cols = n_envs * n_agents;
-  if (n_steps <= 0 || cols <= 0) return hipSuccess;
+hipError_t launch_gae(const float* reward, const float* values, const float* boot, const uint8_t* done,
+                      const GaeShape& g, float* adv, float* ret, hipStream_t s) {
+  const long long cols = g.n_envs * g.n_agents;
+  if (g.n_steps <= 0 || cols <= 0) return hipSuccess;
   const int B = 256;
-  const float gl = gamma * lambda;  // one float32 multiply
+  const float gl = g.gamma * g.lambda;  // one float32 multiply
   hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((cols + B - 1) / B)), dim3(B), 0, s, reward, values, boot, done,
-                     n_steps, n_envs, n_agents, gamma, gl, adv, ret);
+                     g.n_steps, g.n_envs, g.n_agents, g.gamma, gl, adv, ret);
   return hipGetLastError();
 }
 

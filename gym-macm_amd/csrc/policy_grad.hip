@@ -39,6 +39,8 @@
 // logits nor dL/dlogits exist in memory; everything after d_L is the code above. The row's stat terms are
 // lane-local float64 sums over the wave's tiles, reduced once per wave through LDS in lane order into the
 // wave's stat partial. A tail lane's d_L is zero and it adds nothing to the stats.
+#include <type_traits>
+
 #include "policy_mlp.hpp"
 #include "ppo_row.hpp"
 
@@ -321,28 +323,25 @@ long long mlp_grad_partials(long long rows) {
   return tiles < kGradMaxPartials ? tiles : kGradMaxPartials;
 }
 
-hipError_t launch_mlp_grad(const float* params, int od, int hidden, int n_hidden, int n_out, const void* obs,
-                           bool obs_f64, long long rows, const float* dout, float* grad, float* workspace,
-                           hipStream_t s) {
-  const int n_params = od * hidden + hidden + (n_hidden == 2 ? hidden * hidden + hidden : 0) + hidden * n_out + n_out;
+// f(OT{}, n_out as an integral_constant): the instantiation of the gradient kernels for a net and obs type
+template <typename F>
+static void with_net_instance(const MlpNet& net, bool obs_f64, F&& f) {
+  using Pol = std::integral_constant<int, kPolicyLogits>;
+  using One = std::integral_constant<int, 1>;
+  if (net.n_out == kPolicyLogits) return obs_f64 ? f(double{}, Pol{}) : f(float{}, Pol{});
+  return obs_f64 ? f(double{}, One{}) : f(float{}, One{});
+}
+
+hipError_t launch_mlp_grad(const MlpNet& net, const void* obs, bool obs_f64, long long rows, const float* dout,
+                           float* grad, float* workspace, hipStream_t s) {
+  const int n_params = net.n_params();
   if (rows <= 0) return hipMemsetAsync(grad, 0, sizeof(float) * n_params, s);
   const int P = (int)mlp_grad_partials(rows);
   const dim3 grid((unsigned)P), block(64);
-  if (n_out == kPolicyLogits) {
-    if (obs_f64)
-      hipLaunchKernelGGL((mlp_grad_kernel<double, kPolicyLogits>), grid, block, 0, s, params, od, hidden, n_hidden,
-                         (const double*)obs, rows, dout, workspace, n_params);
-    else
-      hipLaunchKernelGGL((mlp_grad_kernel<float, kPolicyLogits>), grid, block, 0, s, params, od, hidden, n_hidden,
-                         (const float*)obs, rows, dout, workspace, n_params);
-  } else {
-    if (obs_f64)
-      hipLaunchKernelGGL((mlp_grad_kernel<double, 1>), grid, block, 0, s, params, od, hidden, n_hidden,
-                         (const double*)obs, rows, dout, workspace, n_params);
-    else
-      hipLaunchKernelGGL((mlp_grad_kernel<float, 1>), grid, block, 0, s, params, od, hidden, n_hidden,
-                         (const float*)obs, rows, dout, workspace, n_params);
-  }
+  with_net_instance(net, obs_f64, [&](auto ot, auto n_out) {
+    hipLaunchKernelGGL((mlp_grad_kernel<decltype(ot), decltype(n_out)::value>), grid, block, 0, s, net.params, net.od,
+                       net.hidden, net.n_hidden, (const decltype(ot)*)obs, rows, dout, workspace, n_params);
+  });
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   hipLaunchKernelGGL(mlp_grad_reduce_kernel, dim3((unsigned)((n_params + 63) / 64)), dim3(256), 0, s, workspace, P,
                      n_params, grad);
@@ -350,27 +349,15 @@ hipError_t launch_mlp_grad(const float* params, int od, int hidden, int n_hidden
 }
 
 // launch_mlp_grad with the loss in the launch; rows > 0 (the caller serves rows = 0)
-hipError_t launch_mlp_ppo_grad(const float* params, int od, int hidden, int n_hidden, int n_out, const void* obs,
-                               bool obs_f64, long long rows, const PpoGradArgs& G, float* grad, float* workspace,
-                               hipStream_t s) {
-  const int n_params = od * hidden + hidden + (n_hidden == 2 ? hidden * hidden + hidden : 0) + hidden * n_out + n_out;
+hipError_t launch_mlp_ppo_grad(const MlpNet& net, const void* obs, bool obs_f64, long long rows, const PpoGradArgs& G,
+                               float* grad, float* workspace, hipStream_t s) {
+  const int n_params = net.n_params();
   const int P = (int)mlp_grad_partials(rows);
   const dim3 grid((unsigned)P), block(64);
-  if (n_out == kPolicyLogits) {
-    if (obs_f64)
-      hipLaunchKernelGGL((mlp_ppo_grad_kernel<double, kPolicyLogits>), grid, block, 0, s, params, od, hidden, n_hidden,
-                         (const double*)obs, rows, G, workspace, n_params);
-    else
-      hipLaunchKernelGGL((mlp_ppo_grad_kernel<float, kPolicyLogits>), grid, block, 0, s, params, od, hidden, n_hidden,
-                         (const float*)obs, rows, G, workspace, n_params);
-  } else {
-    if (obs_f64)
-      hipLaunchKernelGGL((mlp_ppo_grad_kernel<double, 1>), grid, block, 0, s, params, od, hidden, n_hidden,
-                         (const double*)obs, rows, G, workspace, n_params);
-    else
-      hipLaunchKernelGGL((mlp_ppo_grad_kernel<float, 1>), grid, block, 0, s, params, od, hidden, n_hidden,
-                         (const float*)obs, rows, G, workspace, n_params);
-  }
+  with_net_instance(net, obs_f64, [&](auto ot, auto n_out) {
+    hipLaunchKernelGGL((mlp_ppo_grad_kernel<decltype(ot), decltype(n_out)::value>), grid, block, 0, s, net.params, net.od,
+                       net.hidden, net.n_hidden, (const decltype(ot)*)obs, rows, G, workspace, n_params);
+  });
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   hipLaunchKernelGGL(mlp_grad_reduce_kernel, dim3((unsigned)((n_params + 63) / 64)), dim3(256), 0, s, workspace, P,
                      n_params, grad);

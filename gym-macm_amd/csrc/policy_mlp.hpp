@@ -155,11 +155,18 @@ __device__ __forceinline__ float value_mlp_row(const ValueArgs& V, int od, const
   return value_mlp_row_t<OT, 4, 16>(p, V.n_hidden, o);
 }
 
-// host side (C++ linkage, macm_capi.hip): the one-shot kernels over rows and the GAE kernel (policy.hip)
+// host side (C++ linkage, capi_learn.hip and capi_world.hip): the one-shot kernels over rows and the GAE kernel (policy.hip)
 hipError_t launch_value_flock(const ValueArgs& V, const void* obs, bool obs_f64, int od, long long rows, float* values,
                               hipStream_t s);
-hipError_t launch_gae(const float* reward, const float* values, const float* boot, const uint8_t* done, int n_steps,
-                      long long n_envs, int n_agents, float gamma, float lambda, float* adv, float* ret, hipStream_t s);
+// (host side) a GAE pass: [K, E, N] rewards, values and boot, [K, E] done flags
+struct GaeShape {
+  int n_steps;
+  long long n_envs;
+  int n_agents;
+  float gamma, lambda;
+};
+hipError_t launch_gae(const float* reward, const float* values, const float* boot, const uint8_t* done,
+                      const GaeShape& g, float* adv, float* ret, hipStream_t s);
 hipError_t launch_policy_flock(const PolicyArgs& M, const void* obs, bool obs_f64, int od, long long rows,
                                uint8_t* act, hipStream_t s);
 
@@ -167,10 +174,19 @@ hipError_t launch_policy_flock(const PolicyArgs& M, const void* obs, bool obs_f6
 // [rows, n_out] (macm_policy_grad / macm_value_grad). One wave writes one partial [n_params] into the
 // workspace, at most kGradMaxPartials of them; kGradMaxParams bounds n_params over the supported shapes.
 constexpr int kGradMaxPartials = 2048;
-constexpr int kGradMaxParams = 6 * 32 + 32 + 32 * 32 + 32 + 32 * kPolicyLogits + kPolicyLogits;  // 1,577
+// floats of a net's params: W1[od][h], b1[h], (W2[h][h], b2[h]), W3[h][n_out], b3[n_out]
+constexpr int mlp_n_params(int od, int hidden, int n_hidden, int n_out) {
+  return od * hidden + hidden + (n_hidden == 2 ? hidden * hidden + hidden : 0) + hidden * n_out + n_out;
+}
+constexpr int kGradMaxParams = mlp_n_params(6, 32, 2, kPolicyLogits);  // 1,577
 long long mlp_grad_partials(long long rows);  // min(ceil(rows / 64), kGradMaxPartials)
-hipError_t launch_mlp_grad(const float* params, int od, int hidden, int n_hidden, int n_out, const void* obs,
-                           bool obs_f64, long long rows, const float* dout, float* grad, float* workspace,
-                           hipStream_t s);
+// Either net as the gradient launches take it (host side; never a kernel parameter)
+struct MlpNet {
+  const float* params;
+  int od, hidden, n_hidden, n_out;
+  int n_params() const { return mlp_n_params(od, hidden, n_hidden, n_out); }
+};
+hipError_t launch_mlp_grad(const MlpNet& net, const void* obs, bool obs_f64, long long rows, const float* dout,
+                           float* grad, float* workspace, hipStream_t s);
 
 }  // namespace macm

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "policy_mlp.hpp"
+
 namespace macm {
 
 // macm_ppo_config without its reserved words
@@ -108,7 +110,7 @@ __device__ __forceinline__ float ppo_value_row(float v, float ret, bool has_old,
   return (float)(k * ((double)cfg.vf_coef * g));
 }
 
-// host side (C++ linkage, macm_capi.hip). ppo_loss.hip: the one-shot kernels and the reduction of the stat
+// host side (C++ linkage, capi_learn.hip). ppo_loss.hip: the one-shot kernels and the reduction of the stat
 // partials; policy_grad.hip: the loss-to-gradient launch of one net.
 constexpr int kPpoBlock = 256;         // ppo_loss_kernel: threads per block, one row per thread and stride
 constexpr int kPpoMaxBlocks = 2048;    // ... and at most this many blocks, one stat partial each
@@ -146,8 +148,7 @@ struct PpoGradArgs {
   double k;                 // 1 / rows
   double* stat;             // [mlp_grad_partials(rows)][kPpoStatSlots], or NULL: no stats wanted, none summed
 };
-hipError_t launch_mlp_ppo_grad(const float* params, int od, int hidden, int n_hidden, int n_out, const void* obs,
-                               bool obs_f64, long long rows, const PpoGradArgs& G, float* grad, float* workspace,
-                               hipStream_t s);
+hipError_t launch_mlp_ppo_grad(const MlpNet& net, const void* obs, bool obs_f64, long long rows, const PpoGradArgs& G,
+                               float* grad, float* workspace, hipStream_t s);
 
 }  // namespace macm

@@ -343,108 +343,52 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
   }
 }
 
-hipError_t launch_env_order(const uint32_t* ccount, uint32_t* order, int E, int C, hipStream_t s, unsigned int* reset2);
-
-template <int MODE, int NCAP, typename OT, bool SCAL = false>
-static void launch_roll_ar(int nsteps, unsigned long long astride, int traj, hipStream_t s, const StepParams& P,
-                           const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB, int cur, const void* actions,
-                           void* obs, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, int reload, uint32_t* mt,
-                           const PoseDraw& D, const FinalOut& F, int32_t* hit_out = nullptr,
-                           const PolicyArgs* policy = nullptr, const ValueArgs* critic = nullptr) {
-  // astride == 0: closed loop, `actions` is the bots' action buffer
-  uint8_t* pol = astride == 0 ? static_cast<uint8_t*>(const_cast<void*>(actions)) : nullptr;
-  if (B.sched && nsteps >= kRollBalanceMinSteps) {  // the balanced env order, as launch_roll
-    if (launch_env_order(reinterpret_cast<const uint32_t*>(B.ccount[cur]), B.sched, P.n_envs, P.max_contacts, s, nullptr) !=
+template <int MODE, int NCAP, typename OT, bool SCAL>
+static void launch_roll_ar(const RolloutArgs<OT>& A, const FlockRollExtras& x, const ResetLaunch& r, int32_t* hit_out,
+                           hipStream_t s) {
+  const StepParams& P = A.P;
+  if (A.B.sched && A.nsteps >= kRollBalanceMinSteps) {  // the balanced env order, as launch_roll
+    if (launch_env_order(reinterpret_cast<const uint32_t*>(A.B.ccount[A.cur]), A.B.sched, P.n_envs, P.max_contacts, s) !=
         hipSuccess)
       return;  // no rollout on a stale order (the caller reports it)
   }
-  RolloutArArgs<OT> R{{P, B, TP, TB, actions, (OT*)obs, nbr, rew, coll, done, astride, cur, nsteps, pol, traj, 0, nullptr,
-                       0u, 0},
-                      mt,
-                      D,
-                      F};
-  if constexpr (MODE == kFlock) {
-    if (!pol) {  // actions given: the carried step
-      if (reload & 1) R.A.cur |= kRollReloadBit;
-      if (NCAP == 64 && (reload & 2)) R.A.cur |= kRollNearPlainBit;
-      hipLaunchKernelGGL((env_rollout_ar_w64<MODE, NCAP, OT, SCAL, true>), dim3(P.n_envs), dim3(W), 0, s, R);
-      return;
-    }
-    if (NCAP == 64 && (reload & 2)) R.A.cur |= kRollNearPlainBit;
-    if (policy && critic) {  // and a registered critic: the kernel that evaluates it beside the actor
-      RolloutArArgs<ObsPolV<OT>> V;
-      static_cast<RolloutArArgs<OT>&>(V) = R;
-      V.pol = *policy;
-      V.val = *critic;
-      hipLaunchKernelGGL((env_rollout_ar_w64<kFlock, NCAP, ObsPolV<OT>, SCAL>), dim3(P.n_envs), dim3(W), 0, s, V);
-      return;
-    }
-    if (policy) {  // a registered policy: the kernel with the MLP where the bot is
-      RolloutArArgs<ObsPol<OT>> V;
-      static_cast<RolloutArArgs<OT>&>(V) = R;
-      V.pol = *policy;
-      hipLaunchKernelGGL((env_rollout_ar_w64<kFlock, NCAP, ObsPol<OT>, SCAL>), dim3(P.n_envs), dim3(W), 0, s, V);
-      return;
-    }
-  } else if (hit_out) {  // events registered: the kernel that records them
-    RolloutArArgs<ObsEv<OT>> V;
+  RolloutArArgs<OT> R{};
+  R.A = A;
+  R.mt = r.mt;
+  R.D = r.D;
+  R.F = r.F;
+  roll_variant<MODE, NCAP, OT>(R.A.cur, A.policy_act != nullptr, x, hit_out, [&](auto tag, auto carry, auto&& fill) {
+    using OTA = typename decltype(tag)::type;
+    RolloutArArgs<OTA> V;
     static_cast<RolloutArArgs<OT>&>(V) = R;
-    V.hit_out = hit_out;
-    hipLaunchKernelGGL((env_rollout_ar_w64<kTdm, NCAP, ObsEv<OT>>), dim3(P.n_envs), dim3(W), 0, s, V);
-    return;
-  }
-  hipLaunchKernelGGL((env_rollout_ar_w64<MODE, NCAP, OT, SCAL>), dim3(P.n_envs), dim3(W), 0, s, R);
+    fill(V);
+    hipLaunchKernelGGL((env_rollout_ar_w64<MODE, NCAP, OTA, SCAL, decltype(carry)::value>), dim3(P.n_envs), dim3(W), 0, s,
+                       V);
+  });
 }
 
-// the same instantiation choice as launch_rollout_w64 / launch_tdm_rollout_w64
-hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int cur, const void* actions, void* obs,
-                                 bool obs_f64, int32_t* nbr, float* rew, uint8_t* coll, uint8_t* done, hipStream_t s,
-                                 int nsteps, unsigned long long astride, int traj, int reload, uint32_t* mt,
-                                 const PoseDraw& D, const FinalOut& F, const PolicyArgs* policy,
-                                 const ValueArgs* critic) {
+hipError_t launch_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, int cur, const FlockIO& io,
+                                 const RollShape& sh, const FlockRollExtras& x, const ResetLaunch& r, hipStream_t s) {
   const TdmParams TP{};
   const TdmBuffers TB{};
-  const bool small = P.n_agents <= 32;
-  if (obs_f64) {
-    if (small)
-      launch_roll_ar<kFlock, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                        reload, mt, D, F, nullptr, policy, critic);
-    else
-      launch_roll_ar<kFlock, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                        reload, mt, D, F, nullptr, policy, critic);
-  } else {
-    if (small)
-      launch_roll_ar<kFlock, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                       reload, mt, D, F, nullptr, policy, critic);
-    else if (P.n_envs >= kScalarSweepMinEnvs)
-      launch_roll_ar<kFlock, 64, float, true>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll,
-                                             done, reload, mt, D, F, nullptr, policy, critic);
-    else
-      launch_roll_ar<kFlock, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nbr, rew, coll, done,
-                                       reload, mt, D, F, nullptr, policy, critic);
-  }
+  with_instance<kFlock>(P, io.obs_f64, [&](auto ncap, auto ot, auto scal) {
+    using OT = decltype(ot);
+    RolloutArgs<OT> A = roll_args<OT>(P, B, TP, TB, cur, io, sh, TailLaunch{});
+    A.nbr_out = io.nbr;
+    A.rew_out = io.rew;
+    A.coll_out = io.coll;
+    launch_roll_ar<kFlock, decltype(ncap)::value, OT, decltype(scal)::value>(A, x, r, nullptr, s);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_tdm_rollout_ar_w64(const StepParams& P, const WorldBuffers& B, const TdmParams& TP,
-                                     const TdmBuffers& TB, int cur, const void* actions, void* obs, bool obs_f64,
-                                     uint8_t* done, hipStream_t s, int nsteps, unsigned long long astride, int traj,
-                                     uint32_t* mt, const PoseDraw& D, const FinalOut& F, int32_t* hit_out) {
-  const bool small = P.n_agents <= 32;
-  if (obs_f64) {
-    if (small)
-      launch_roll_ar<kTdm, 32, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                      nullptr, done, 0, mt, D, F, hit_out);
-    else
-      launch_roll_ar<kTdm, 64, double>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                      nullptr, done, 0, mt, D, F, hit_out);
-  } else {
-    if (small)
-      launch_roll_ar<kTdm, 32, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                     nullptr, done, 0, mt, D, F, hit_out);
-    else
-      launch_roll_ar<kTdm, 64, float>(nsteps, astride, traj, s, P, B, TP, TB, cur, actions, obs, nullptr, nullptr,
-                                     nullptr, done, 0, mt, D, F, hit_out);
-  }
+                                     const TdmBuffers& TB, int cur, const TdmIO& io, const RollShape& sh,
+                                     const ResetLaunch& r, hipStream_t s) {
+  with_instance<kTdm>(P, io.obs_f64, [&](auto ncap, auto ot, auto scal) {
+    using OT = decltype(ot);
+    launch_roll_ar<kTdm, decltype(ncap)::value, OT, decltype(scal)::value>(
+        roll_args<OT>(P, B, TP, TB, cur, io, sh, TailLaunch{}), FlockRollExtras{}, r, io.hit_out, s);
+  });
   return hipGetLastError();
 }

@@ -14,6 +14,7 @@
 // arithmetic), each direction's own quadrant, "- angle" and wrap, p = wrap(aj - ai), r =
 // obs_sqrt<OT> of the same float32 distance.
 #include "flock_common.hpp"
+#include "launch.hpp"
 #include "tdm_obs.hpp"
 
 namespace macm {

@@ -21,10 +21,12 @@
 
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 #include "flock_common.hpp"
 #include "tdm_obs.hpp"
 #include "flock_spill.hpp"
+#include "launch.hpp"
 
 namespace macm {
 namespace tdmwg {
@@ -215,7 +217,7 @@ __global__ __launch_bounds__(1024) void tdm_observe_wg(StepParams P, WorldBuffer
                       s_c, s_a);
 }
 
-// ---- host-side launchers (C++ linkage, used by macm_capi.hip) -------------------------------------
+// ---- host-side launchers (declared in launch.hpp) --------------------------------------------------
 static int tdm_wg_block(int N) { return N > 1024 ? 1024 : ((N + 63) / 64) * 64; }
 
 // as wg_configure: the kernels' dynamic-LDS limits only grow (per device)
@@ -246,33 +248,25 @@ hipError_t tdm_wg_configure(int N) {
 }
 
 hipError_t launch_tdm_step_wg(const StepParams& P, const WorldBuffers& B, const TdmParams& TP, const TdmBuffers& TB,
-                              int cur, const void* actions, void* obs, bool obs_f64, uint8_t* done, hipStream_t s,
-                              int32_t* hit_out) {
+                              int cur, const TdmIO& io, hipStream_t s) {
   const dim3 grid(P.n_envs), block(tdm_wg_block(P.n_agents));
   const int lds = tdm_wg_step_lds(P.n_agents);
-  const int bpt = P.n_agents <= 1024 ? 1 : P.n_agents <= 2048 ? 2 : 4;
-  const uchar4* a = (const uchar4*)actions;
-  if (hit_out) {  // events registered: the kernels that record them
-    if (obs_f64) {
-      if (bpt == 1) hipLaunchKernelGGL((tdm_step_ev_wg<double, 1>), grid, block, lds, s, P, B, TP, TB, cur, a, (double*)obs, done, hit_out);
-      else if (bpt == 2) hipLaunchKernelGGL((tdm_step_ev_wg<double, 2>), grid, block, lds, s, P, B, TP, TB, cur, a, (double*)obs, done, hit_out);
-      else hipLaunchKernelGGL((tdm_step_ev_wg<double, 4>), grid, block, lds, s, P, B, TP, TB, cur, a, (double*)obs, done, hit_out);
-    } else {
-      if (bpt == 1) hipLaunchKernelGGL((tdm_step_ev_wg<float, 1>), grid, block, lds, s, P, B, TP, TB, cur, a, (float*)obs, done, hit_out);
-      else if (bpt == 2) hipLaunchKernelGGL((tdm_step_ev_wg<float, 2>), grid, block, lds, s, P, B, TP, TB, cur, a, (float*)obs, done, hit_out);
-      else hipLaunchKernelGGL((tdm_step_ev_wg<float, 4>), grid, block, lds, s, P, B, TP, TB, cur, a, (float*)obs, done, hit_out);
-    }
-    return hipGetLastError();
-  }
-  if (obs_f64) {
-    if (bpt == 1) hipLaunchKernelGGL((tdm_step_wg<double, 1>), grid, block, lds, s, P, B, TP, TB, cur, a, (double*)obs, done);
-    else if (bpt == 2) hipLaunchKernelGGL((tdm_step_wg<double, 2>), grid, block, lds, s, P, B, TP, TB, cur, a, (double*)obs, done);
-    else hipLaunchKernelGGL((tdm_step_wg<double, 4>), grid, block, lds, s, P, B, TP, TB, cur, a, (double*)obs, done);
-  } else {
-    if (bpt == 1) hipLaunchKernelGGL((tdm_step_wg<float, 1>), grid, block, lds, s, P, B, TP, TB, cur, a, (float*)obs, done);
-    else if (bpt == 2) hipLaunchKernelGGL((tdm_step_wg<float, 2>), grid, block, lds, s, P, B, TP, TB, cur, a, (float*)obs, done);
-    else hipLaunchKernelGGL((tdm_step_wg<float, 4>), grid, block, lds, s, P, B, TP, TB, cur, a, (float*)obs, done);
-  }
+  const uchar4* a = (const uchar4*)io.actions;
+  // bodies per thread 1, 2 or 4; events registered: the kernels that record them
+  const auto go = [&](auto ot, auto bpt) {
+    using OT = decltype(ot);
+    constexpr int BPT = decltype(bpt)::value;
+    if (io.hit_out)
+      hipLaunchKernelGGL((tdm_step_ev_wg<OT, BPT>), grid, block, lds, s, P, B, TP, TB, cur, a, (OT*)io.obs, io.done,
+                         io.hit_out);
+    else
+      hipLaunchKernelGGL((tdm_step_wg<OT, BPT>), grid, block, lds, s, P, B, TP, TB, cur, a, (OT*)io.obs, io.done);
+  };
+  with_obs_type(io.obs_f64, [&](auto ot) {
+    if (P.n_agents <= 1024) go(ot, std::integral_constant<int, 1>{});
+    else if (P.n_agents <= 2048) go(ot, std::integral_constant<int, 2>{});
+    else go(ot, std::integral_constant<int, 4>{});
+  });
   return hipGetLastError();
 }
 
@@ -280,10 +274,9 @@ hipError_t launch_tdm_init_wg(const StepParams& P, const WorldBuffers& B, const 
                               int cur, void* obs, bool obs_f64, const uint8_t* mask, hipStream_t s) {
   const dim3 grid(P.n_envs), block(tdm_wg_block(P.n_agents));
   const int lds = tdm_wg_obs_lds(P.n_agents);
-  if (obs_f64)
-    hipLaunchKernelGGL(tdm_init_wg<double>, grid, block, lds, s, P, B, TP, TB, cur, (double*)obs, mask);
-  else
-    hipLaunchKernelGGL(tdm_init_wg<float>, grid, block, lds, s, P, B, TP, TB, cur, (float*)obs, mask);
+  with_obs_type(obs_f64, [&](auto ot) {
+    hipLaunchKernelGGL(tdm_init_wg<decltype(ot)>, grid, block, lds, s, P, B, TP, TB, cur, (decltype(ot)*)obs, mask);
+  });
   return hipGetLastError();
 }
 
@@ -291,10 +284,9 @@ hipError_t launch_tdm_observe_wg(const StepParams& P, const WorldBuffers& B, con
                                  const TdmBuffers& TB, void* obs, bool obs_f64, hipStream_t s) {
   const dim3 grid(P.n_envs), block(tdm_wg_block(P.n_agents));
   const int lds = tdm_wg_obs_lds(P.n_agents);
-  if (obs_f64)
-    hipLaunchKernelGGL(tdm_observe_wg<double>, grid, block, lds, s, P, B, TP, TB, (double*)obs);
-  else
-    hipLaunchKernelGGL(tdm_observe_wg<float>, grid, block, lds, s, P, B, TP, TB, (float*)obs);
+  with_obs_type(obs_f64, [&](auto ot) {
+    hipLaunchKernelGGL(tdm_observe_wg<decltype(ot)>, grid, block, lds, s, P, B, TP, TB, (decltype(ot)*)obs);
+  });
   return hipGetLastError();
 }
 

@@ -133,7 +133,7 @@ def test_flock_wave_spill_partial_outputs(subset):
 @pytest.mark.parametrize("debug", [0, _abi.DEBUG_FORCE_SPILL], ids=["fast", "spill"])
 @pytest.mark.parametrize("subset", FLOCK_SUBSETS, ids=ids(FLOCK_SUBSETS))
 def test_flock_workgroup_partial_outputs(subset, debug):
-    """The workgroup path (flock_step_wg.hip kernel C's guards; macm_capi.hip step_outputs' rows of the
+    """The workgroup path (flock_step_wg.hip kernel C's guards; capi_world.hip step_outputs' rows of the
     trajectory form) at N = 100: a block of 128 threads, 28 of them without a body in every env. Once
     with every env in the spill step (kernel A's call of flock_spill.hpp step_env)."""
     E = 3
@@ -146,7 +146,7 @@ def test_flock_workgroup_partial_outputs(subset, debug):
 
 @pytest.mark.parametrize("subset", [("reward",), ("reward", "done")], ids=["reward", "reward+done"])
 def test_flock_sliced_rollout_partial_outputs(subset):
-    """The workgroup path's rollout in env slices on streams of their own (macm_capi.hip
+    """The workgroup path's rollout in env slices on streams of their own (capi_world.hip
     rollout_wg_slices: `row(p, per_env)` keeps a NULL field NULL for every slice, step_outputs for every
     step), 1031 envs: uneven slices."""
     E, N, K = 1031, 100, 4
@@ -224,7 +224,7 @@ def test_tdm_wave_partial_outputs(monkeypatch, form, subset):
     """The TDM wave kernel (flock_step_w64.hip: `if (TB.health_out)`, `if (TB.alive_out)`,
     `if (TB.winner_out)`, `if (done_out)`, the rollout's traj_row; tdm_obs.hpp: `if (obs)` / `if (mask)`
     of every store) with the observation fused into the step, split off (tdm_obs_snap.hip: `o` / `m`
-    NULL; macm_capi.hip tdm_rollout_split's row()) and in the launch's tail (tdm_tail_row's obs_r /
+    NULL; capi_tdm.hip tdm_rollout_split's row()) and in the launch's tail (tdm_tail_row's obs_r /
     mask_r), at [8, 8]. obs without mask and mask without obs take the observation path with one of the
     two NULL; the subsets without either must skip it."""
     E, teams, K = 4, [8, 8], 5
@@ -248,7 +248,7 @@ def test_tdm_wave_partial_outputs(monkeypatch, form, subset):
 @pytest.mark.parametrize("subset", TDM_SUBSETS, ids=ids(TDM_SUBSETS))
 def test_tdm_workgroup_partial_outputs(subset):
     """The workgroup TDM step (tdm_step_wg.hip: `if (TB.health_out)`, `if (TB.alive_out)`,
-    `if (TB.winner_out)`; flock_spill.hpp step_env's TDM env layer and tdm_obs_block; macm_capi.hip
+    `if (TB.winner_out)`; flock_spill.hpp step_env's TDM env layer and tdm_obs_block; capi_tdm.hip
     tdm_rollout's row() per step) at [33, 32]: 65 agents on a block of 128 threads."""
     E = 2
     w, t = tdm_worlds(E, [33, 32], 9, world_width=14.0, world_height=14.0)
@@ -361,7 +361,7 @@ def test_tdm_reset_place_reset_envs_partial_outputs(E, teams, subset):
 
 def test_flock_required_outputs_are_refused_on_the_host():
     """Flock's reward is required by step and every rollout form, obs by the closed loop (the bots act
-    on it): MACM_E_INVALID from the host checks (macm_capi.hip macm_world_step, world_rollout), nothing
+    on it): MACM_E_INVALID from the host checks (capi_world.hip macm_world_step, world_rollout), nothing
     launched: state, step counts and counters as before, every buffer untouched."""
     E, N, K = 3, 20, 2
     w, _ = flock_worlds(E, N, 1)

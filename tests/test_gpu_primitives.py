@@ -185,7 +185,7 @@ def test_obs_sqrt(probe, ot):
 
 
 def invariant_K(radius, density):
-    """K = mA + mB of two equal bodies, inv_mass in float32 as macm_capi.hip fill_body_params derives it."""
+    """K = mA + mB of two equal bodies, inv_mass in float32 as capi_common.hpp fill_body_params derives it."""
     r, d = np.float32(radius), np.float32(density)
     mass = d * np.float32(3.14159265359) * r * r
     inv = np.float32(1.0) / mass

@@ -10,7 +10,7 @@ git archive "$COMMIT" gym-macm_amd/csrc include | tar -x -C "$D"
 mkdir -p "$D/build"
 for f in "$D"/gym-macm_amd/csrc/*.hip; do
   b=$(basename "$f" .hip)
-  X=""; [ "$b" = flock_rollout_w64 ] && X="-mllvm -disable-machine-licm"  # as the Makefile
+  X=""; { [ "$b" = flock_rollout_w64 ] || [ "$b" = flock_rollout_ar_w64 ]; } && X="-mllvm -disable-machine-licm"  # as the Makefile
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -Wall \
     -Wno-unused-result $X "$@" -c -o "$D/build/$b.o" "$f" &
 done

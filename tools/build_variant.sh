@@ -7,11 +7,11 @@ cd "$(dirname "$0")/.."
 NAME=$1; shift
 mkdir -p abv/build_$NAME
 PIDS=()
-SRC="flock_step_w64 flock_rollout_w64 flock_step_wg flock_big tdm_step_wg bots env_reset actions_check macm_capi"
-for f in $SRC; do
-  X=""; [ $f = flock_rollout_w64 ] && X="-mllvm -disable-machine-licm"  # as the Makefile
+for src in gym-macm_amd/csrc/*.hip; do  # every unit, as tools/isa_snapshot.sh
+  f=$(basename "$src" .hip)
+  X=""; { [ $f = flock_rollout_w64 ] || [ $f = flock_rollout_ar_w64 ]; } && X="-mllvm -disable-machine-licm"  # as the Makefile
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -Wall -Wno-unused-result $X "$@" \
-    -c -o abv/build_$NAME/$f.o gym-macm_amd/csrc/$f.hip &
+    -c -o abv/build_$NAME/$f.o "$src" &
   PIDS+=($!)
 done
 for p in "${PIDS[@]}"; do wait "$p" || { echo "compile failed: abv/$NAME.so not built" >&2; rm -rf abv/build_$NAME; exit 1; }; done
