@@ -176,10 +176,12 @@ int macm_ppo_loss(const macm_ppo_config* cfg, int64_t rows, const float* logits,
   return MACM_OK;
 }
 
-int macm_ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c, const void* obs,
-                  int32_t obs_f64, int64_t rows, const uint8_t* actions, const float* old_logp, const float* adv,
-                  const float* ret, const float* old_values, float* grad_policy, float* grad_value, double* stats,
-                  void* workspace, int64_t workspace_bytes, void* stream) {
+// macm_ppo_grad (R NULL) and macm_ppo_grad_rows (R: the index and the advantage's normalisation) behind
+// the latter's own checks
+static int ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c, const void* obs,
+                    int32_t obs_f64, int64_t rows, const PpoRowsArgs* R, const uint8_t* actions, const float* old_logp,
+                    const float* adv, const float* ret, const float* old_values, float* grad_policy,
+                    float* grad_value, double* stats, void* workspace, int64_t workspace_bytes, void* stream) {
   if (const int rc = ppo_check(cfg, rows, c && old_values, stats, workspace, workspace_bytes)) return rc;
   if (!p && !c) return fail(MACM_E_INVALID, "ppo: policy and critic are both NULL");
   if (p) {
@@ -207,12 +209,62 @@ int macm_ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const ma
   const PpoCfg k{cfg->clip, cfg->vf_coef, cfg->ent_coef, cfg->vf_clip};
   double* const part = stats ? reinterpret_cast<double*>((char*)workspace + ppo_stat_offset(rows)) : nullptr;
   const PpoGradArgs G{actions, old_logp, adv, ret, c ? old_values : nullptr, k, 1.0 / (double)rows, part};
-  if (p)
-    HIP_TRY(launch_mlp_ppo_grad(net_of(p, kPolicyLogits), obs, obs_f64 != 0, rows, G, grad_policy, (float*)workspace, s));
-  if (c)
-    HIP_TRY(launch_mlp_ppo_grad(net_of(c, 1), obs, obs_f64 != 0, rows, G, grad_value, (float*)workspace, s));
+  const auto launch = [&](const MlpNet& net, float* grad) {
+    return R ? launch_mlp_ppo_grad_rows(net, obs, obs_f64 != 0, rows, G, *R, grad, (float*)workspace, s)
+             : launch_mlp_ppo_grad(net, obs, obs_f64 != 0, rows, G, grad, (float*)workspace, s);
+  };
+  if (p) HIP_TRY(launch(net_of(p, kPolicyLogits), grad_policy));
+  if (c) HIP_TRY(launch(net_of(c, 1), grad_value));
   if (stats)
     HIP_TRY(launch_ppo_stats(part, (int)mlp_grad_partials(rows), rows, k, p != nullptr, c != nullptr, stats, s));
+  return MACM_OK;
+}
+
+int macm_ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c, const void* obs,
+                  int32_t obs_f64, int64_t rows, const uint8_t* actions, const float* old_logp, const float* adv,
+                  const float* ret, const float* old_values, float* grad_policy, float* grad_value, double* stats,
+                  void* workspace, int64_t workspace_bytes, void* stream) {
+  return ppo_grad(cfg, p, c, obs, obs_f64, rows, nullptr, actions, old_logp, adv, ret, old_values, grad_policy,
+                  grad_value, stats, workspace, workspace_bytes, stream);
+}
+
+// The source rows of an index: at most what an int32 index can name
+static int n_src_check(int64_t n_src) {
+  if (n_src < 0 || n_src > (int64_t)INT32_MAX)
+    return fail(MACM_E_INVALID, "ppo: n_src must be in [0, 2^31 - 1], got " + std::to_string(n_src));
+  return MACM_OK;
+}
+
+int macm_ppo_grad_rows(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c, const void* obs,
+                       int32_t obs_f64, int64_t rows, const int32_t* index, int64_t n_src, const double* adv_norm,
+                       const uint8_t* actions, const float* old_logp, const float* adv, const float* ret,
+                       const float* old_values, float* grad_policy, float* grad_value, double* stats, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  if (!index && !adv_norm)
+    return fail(MACM_E_INVALID, "ppo: index and adv_norm are both NULL (that call is macm_ppo_grad)");
+  if (const int rc = n_src_check(n_src)) return rc;
+  if (misaligned(index, 4)) return fail(MACM_E_INVALID, "ppo: index must be 4-byte aligned");
+  if (misaligned(adv_norm, 8)) return fail(MACM_E_INVALID, "ppo: adv_norm must be 8-byte aligned");
+  const PpoRowsArgs R{index, n_src, adv_norm};
+  return ppo_grad(cfg, p, c, obs, obs_f64, rows, &R, actions, old_logp, adv, ret, old_values, grad_policy, grad_value,
+                  stats, workspace, workspace_bytes, stream);
+}
+
+int macm_adv_moments(const float* x, const int32_t* index, int64_t n_src, int64_t rows, double eps, double* out,
+                     void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!x || !out) return fail(MACM_E_INVALID, "moments: x/out is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "moments: rows must be >= 0");
+  if (const int rc = n_src_check(n_src)) return rc;
+  if (!(eps >= 0.0) || std::isinf(eps)) return fail(MACM_E_INVALID, "moments: eps must be finite and >= 0");
+  if (misaligned(x, 4) || misaligned(index, 4))
+    return fail(MACM_E_INVALID, "moments: x and index must be 4-byte aligned");
+  if (misaligned(out, 8)) return fail(MACM_E_INVALID, "moments: out must be 8-byte aligned");
+  if (rows > 0 && !workspace) return fail(MACM_E_INVALID, "moments: workspace is NULL");
+  if (rows > 0 && misaligned(workspace, 16)) return fail(MACM_E_INVALID, "moments: workspace must be 16-byte aligned");
+  if (rows > 0 && workspace_bytes < ppo_workspace_bytes(rows))
+    return fail(MACM_E_INVALID, "moments: workspace_bytes " + std::to_string(workspace_bytes) + " is below the " +
+                                    std::to_string(ppo_workspace_bytes(rows)) + " of macm_ppo_workspace");
+  HIP_TRY(launch_adv_moments(x, index, n_src, rows, eps, out, (double*)workspace, (hipStream_t)stream));
   return MACM_OK;
 }
 

@@ -39,6 +39,12 @@
 // logits nor dL/dlogits exist in memory; everything after d_L is the code above. The row's stat terms are
 // lane-local float64 sums over the wave's tiles, reduced once per wave through LDS in lane order into the
 // wave's stat partial. A tail lane's d_L is zero and it adds nothing to the stats.
+//
+// Row-indexed launches (macm_ppo_grad_rows): the same body with DoutPpoRows, in kernels of their own. Lane l
+// of tile t is position r = 64 t + l as before and reads source row s = index[r] of obs and of the loss's
+// inputs; a position whose s is outside [0, n_src) becomes a tail lane before anything is addressed with
+// it. The advantage is normalised in float64 as it is loaded. Tiles, waves, partials and every sum stay
+// functions of the position: the outputs have the bits of macm_ppo_grad on gathered copies.
 #include <type_traits>
 
 #include "policy_mlp.hpp"
@@ -49,11 +55,21 @@ namespace macm {
 // Where d_L comes from: the caller's dout [rows, NOUT], or the PPO loss of the forward's own outputs
 struct DoutMem {
   static constexpr bool kMem = true;  // (the body's dout argument)
+  static constexpr bool kRows = false;
 };
 struct DoutPpo {
   static constexpr bool kMem = false;
+  static constexpr bool kRows = false;
   PpoGradArgs G;
 };
+// ... of source row index[r] in the place of row r, with the advantage normalised on the way in
+struct DoutPpoRows {
+  static constexpr bool kMem = false;
+  static constexpr bool kRows = true;
+  PpoGradArgs G;
+  PpoRowsArgs R;
+};
+using norm_cptr = const __attribute__((address_space(4))) double*;  // adv_norm: wave-uniform scalar loads
 
 using grad_f32x16 = __attribute__((ext_vector_type(16))) float;
 constexpr int kGradLds = 33;  // floats per row of an LDS operand image: 32 columns and one of padding
@@ -115,20 +131,30 @@ __device__ __forceinline__ void grad_store_bias(float* __restrict__ sm, const fl
   }
 }
 
-// d3 and the stat terms of the lane's row r from the last hidden activation: the output layer, then the loss
-template <int H, int NOUT>
+// d3 and the stat terms of the lane's row r (where the lane is live) from the last hidden activation: the
+// output layer, then the loss
+template <int H, int NOUT, typename Src>
 __device__ __forceinline__ void grad_ppo_dout(policy_cptr W3, policy_cptr b3, const float (&h)[H], long long r,
-                                              long long rows, const PpoGradArgs& G, float (&d3)[NOUT],
+                                              bool live, const Src& src, float (&d3)[NOUT],
                                               double (&st)[kPpoPolicyTerms]) {
+  const PpoGradArgs& G = src.G;
   float y[NOUT];
   policy_layer<H, NOUT, false>(W3, b3, h, y);
-  if (r < rows) {
+  if (live) {
     if constexpr (NOUT == kPolicyLogits) {
       uint8_t a[3];
 #pragma unroll
       for (int q = 0; q < 3; ++q) a[q] = G.actions[r * 3 + q];
+      const float old_logp = G.old_logp[r];
+      float adv = G.adv[r];
+      if constexpr (Src::kRows) {
+        if (src.R.norm) {  // (wave-uniform)
+          const norm_cptr nm = (norm_cptr)(unsigned long long)src.R.norm;
+          adv = (float)(((double)adv - nm[0]) * nm[1]);
+        }
+      }
       PpoPolicyTerms T;
-      ppo_policy_row(y, a, G.old_logp[r], G.adv[r], G.cfg, G.k, d3, T);
+      ppo_policy_row(y, a, old_logp, adv, G.cfg, G.k, d3, T);
       st[kPpoPl] = st[kPpoPl] + T.pl;
       st[kPpoH] = st[kPpoH] + T.H;
       st[kPpoKl] = st[kPpoKl] + T.kl;
@@ -168,13 +194,20 @@ __device__ __forceinline__ void mlp_grad_body(policy_cptr p, const OT* __restric
   for (int j = 0; j < NOUT; ++j) bs3[j] = 0.0f;
 
   for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
-    const long long r = t * 64 + lane;
+    long long r = t * 64 + lane;  // the lane's position, and from here on the row it reads
+    bool live = r < rows;
+    if constexpr (Src::kRows) {
+      if (src.R.index) {  // (wave-uniform) a source row outside the arrays: a tail lane, never an address
+        r = live ? (long long)src.R.index[r] : -1;
+        live = (unsigned long long)r < (unsigned long long)src.R.n_src;
+      }
+    }
     float x[OD], d3[NOUT];
 #pragma unroll
     for (int q = 0; q < OD; ++q) x[q] = 0.0f;
 #pragma unroll
     for (int j = 0; j < NOUT; ++j) d3[j] = 0.0f;
-    if (r < rows) {
+    if (live) {
 #pragma unroll
       for (int q = 0; q < OD; ++q) x[q] = (float)obs[r * OD + q];
       if constexpr (Src::kMem) {
@@ -187,11 +220,11 @@ __device__ __forceinline__ void mlp_grad_body(policy_cptr p, const OT* __restric
     if constexpr (NH == 2) {
       float h2[H];
       policy_layer<H, H, true>(W2, b2, h1, h2);
-      if constexpr (!Src::kMem) grad_ppo_dout<H, NOUT>(W3, b3, h2, r, rows, src.G, d3, st);
+      if constexpr (!Src::kMem) grad_ppo_dout<H, NOUT>(W3, b3, h2, r, live, src, d3, st);
       grad_outer<H, NOUT>(sA, sB, h2, d3, acc3, lane);
       grad_back_layer<H, NOUT>(W3, h2, d3, dtop);
     } else {
-      if constexpr (!Src::kMem) grad_ppo_dout<H, NOUT>(W3, b3, h1, r, rows, src.G, d3, st);
+      if constexpr (!Src::kMem) grad_ppo_dout<H, NOUT>(W3, b3, h1, r, live, src, d3, st);
       grad_outer<H, NOUT>(sA, sB, h1, d3, acc3, lane);
       grad_back_layer<H, NOUT>(W3, h1, d3, dtop);
     }
@@ -299,6 +332,37 @@ __global__ __launch_bounds__(64) void mlp_ppo_grad_kernel(const float* __restric
 #undef MACM_GRAD_BODY
 }
 
+// The same launch again with the rows read through an index and the advantage normalised on the way in
+// (macm_ppo_grad_rows): kernels of their own, so that the two above stay what they are
+template <typename OT, int NOUT>
+__global__ __launch_bounds__(64) void mlp_ppo_grad_rows_kernel(const float* __restrict__ params, int od, int hidden,
+                                                               int n_hidden, const OT* __restrict__ obs,
+                                                               long long rows, const PpoGradArgs G,
+                                                               const PpoRowsArgs R, float* __restrict__ partials,
+                                                               int n_params) {
+  __shared__ __attribute__((aligned(16))) float sA[64 * kGradLds];
+  __shared__ float sB[64 * kGradLds];
+  const policy_cptr p = (policy_cptr)(unsigned long long)params;
+  float* const part = partials + (size_t)blockIdx.x * n_params;
+  const DoutPpoRows src{G, R};
+#define MACM_GRAD_BODY(OD_, H_, NH_) \
+  mlp_grad_body<OT, OD_, H_, NH_, NOUT, DoutPpoRows>(p, obs, rows, nullptr, part, sA, sB, src)
+  if (od == 6) {
+    if (hidden == 32) {
+      if (n_hidden == 2) MACM_GRAD_BODY(6, 32, 2); else MACM_GRAD_BODY(6, 32, 1);
+    } else {
+      if (n_hidden == 2) MACM_GRAD_BODY(6, 16, 2); else MACM_GRAD_BODY(6, 16, 1);
+    }
+  } else {
+    if (hidden == 32) {
+      if (n_hidden == 2) MACM_GRAD_BODY(4, 32, 2); else MACM_GRAD_BODY(4, 32, 1);
+    } else {
+      if (n_hidden == 2) MACM_GRAD_BODY(4, 16, 2); else MACM_GRAD_BODY(4, 16, 1);
+    }
+  }
+#undef MACM_GRAD_BODY
+}
+
 // grad[i] = the sum of partials[q][i] over q in index order: thread (run g, column c) sums the g-th
 // quarter of the partials in float64, then run 0's thread adds the four run sums in order and rounds once
 __global__ __launch_bounds__(256) void mlp_grad_reduce_kernel(const float* __restrict__ partials, int n_part,
@@ -357,6 +421,23 @@ hipError_t launch_mlp_ppo_grad(const MlpNet& net, const void* obs, bool obs_f64,
   with_net_instance(net, obs_f64, [&](auto ot, auto n_out) {
     hipLaunchKernelGGL((mlp_ppo_grad_kernel<decltype(ot), decltype(n_out)::value>), grid, block, 0, s, net.params, net.od,
                        net.hidden, net.n_hidden, (const decltype(ot)*)obs, rows, G, workspace, n_params);
+  });
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  hipLaunchKernelGGL(mlp_grad_reduce_kernel, dim3((unsigned)((n_params + 63) / 64)), dim3(256), 0, s, workspace, P,
+                     n_params, grad);
+  return hipGetLastError();
+}
+
+// launch_mlp_ppo_grad through an index and with the advantage's normalisation: the same grid and reduction
+hipError_t launch_mlp_ppo_grad_rows(const MlpNet& net, const void* obs, bool obs_f64, long long rows,
+                                    const PpoGradArgs& G, const PpoRowsArgs& R, float* grad, float* workspace,
+                                    hipStream_t s) {
+  const int n_params = net.n_params();
+  const int P = (int)mlp_grad_partials(rows);
+  const dim3 grid((unsigned)P), block(64);
+  with_net_instance(net, obs_f64, [&](auto ot, auto n_out) {
+    hipLaunchKernelGGL((mlp_ppo_grad_rows_kernel<decltype(ot), decltype(n_out)::value>), grid, block, 0, s, net.params,
+                       net.od, net.hidden, net.n_hidden, (const decltype(ot)*)obs, rows, G, R, workspace, n_params);
   });
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   hipLaunchKernelGGL(mlp_grad_reduce_kernel, dim3((unsigned)((n_params + 63) / 64)), dim3(256), 0, s, workspace, P,

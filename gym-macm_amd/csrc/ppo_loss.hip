@@ -11,6 +11,9 @@
 // ppo_stats_kernel sums the partials in index order within 64 contiguous runs and then the run sums in
 // order, and turns the sums into stats[8]. The grid is a function of `rows` alone, so the same inputs
 // give the same bits on every call and stream.
+//
+// macm_adv_moments (below the stats kernel): the mean and unbiased std of a minibatch's advantages, read
+// through the same index list as macm_ppo_grad_rows, with the same grid and association of the sums.
 #include "ppo_row.hpp"
 
 namespace macm {
@@ -138,6 +141,100 @@ __global__ __launch_bounds__(kPpoRuns * kPpoStatSlots) void ppo_stats_kernel(con
     stats[6] = tot[kPpoRatioMax];
     stats[7] = n;
   }
+}
+
+// ---- macm_adv_moments: mean and unbiased std of x[index[r]] in two passes, four small launches ------------
+// adv_sum_kernel<0> sums x and counts the positions that count, adv_finish_kernel<0> writes out[0] = mean and
+// out[3] = n; adv_sum_kernel<1> sums (x - mean)^2 with that mean, adv_finish_kernel<1> writes out[2] = std and
+// out[1] = rstd. The grid and the sums' association are ppo_loss_kernel's: lane-local over the grid's stride,
+// a wave's lanes in lane order, the block's four waves in order, partial b by block b; the finish kernels sum
+// the partials in index order within 64 contiguous runs and then the run sums in order. All float64, each
+// operation rounded once; a position whose source row is outside [0, n_src) is skipped before x is addressed.
+template <int PASS>
+__global__ __launch_bounds__(kPpoBlock) void adv_sum_kernel(const float* __restrict__ x,
+                                                            const int32_t* __restrict__ index, long long n_src,
+                                                            long long rows, const double* __restrict__ out,
+                                                            double* __restrict__ part) {
+  __shared__ double sm[2][kPpoBlock];
+  __shared__ double wave[2][kPpoBlock / 64];
+  const int tid = threadIdx.x;
+  const double mean = PASS ? out[0] : 0.0;
+  double a = 0.0, n = 0.0;
+  const long long stride = (long long)gridDim.x * kPpoBlock;
+  for (long long r = (long long)blockIdx.x * kPpoBlock + tid; r < rows; r += stride) {
+    long long s = r;
+    if (index) {  // (block-uniform)
+      s = (long long)index[r];
+      if ((unsigned long long)s >= (unsigned long long)n_src) continue;
+    }
+    const double v = (double)x[s];
+    if (PASS == 0) {
+      a = a + v;
+      n = n + 1.0;
+    } else {
+      const double d = v - mean;
+      a = a + d * d;
+    }
+  }
+  sm[0][tid] = a;
+  sm[1][tid] = n;
+  __syncthreads();
+  if (tid < 2 * (kPpoBlock / 64)) {  // thread (term q, wave w): the wave's lanes in lane order
+    const int q = tid / (kPpoBlock / 64), w = tid % (kPpoBlock / 64);
+    double s = 0.0;
+    for (int l = 0; l < 64; ++l) s = s + sm[q][w * 64 + l];
+    wave[q][w] = s;
+  }
+  __syncthreads();
+  if (tid < 2) {
+    double s = 0.0;
+    for (int w = 0; w < kPpoBlock / 64; ++w) s = s + wave[tid][w];
+    part[(size_t)blockIdx.x * 2 + tid] = s;
+  }
+}
+
+constexpr int kAdvRuns = 64;
+template <int PASS>
+__global__ __launch_bounds__(2 * kAdvRuns) void adv_finish_kernel(const double* __restrict__ part, int n_part,
+                                                                  double eps, double* __restrict__ out) {
+  __shared__ double run[2][kAdvRuns];
+  const int q = threadIdx.x & 1, g = threadIdx.x >> 1;
+  const int per = (n_part + kAdvRuns - 1) / kAdvRuns;
+  const int lo = g * per, hi = lo + per < n_part ? lo + per : n_part;
+  double s = 0.0;
+  if (PASS == 0 || q == 0) {  // (the second pass has no count)
+#pragma unroll 4
+    for (int i = lo; i < hi; ++i) s = s + part[(size_t)i * 2 + q];
+  }
+  run[q][g] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0, n = 0.0;
+    for (int i = 0; i < kAdvRuns; ++i) {
+      a = a + run[0][i];
+      n = n + run[1][i];
+    }
+    if (PASS == 0) {
+      out[0] = n > 0.0 ? a / n : 0.0;
+      out[3] = n;
+    } else {
+      n = out[3];
+      const double sd = sqrt(n > 1.0 ? a / (n - 1.0) : 0.0);
+      out[1] = 1.0 / (sd + eps);
+      out[2] = sd;
+    }
+  }
+}
+
+hipError_t launch_adv_moments(const float* x, const int32_t* index, long long n_src, long long rows, double eps,
+                              double* out, double* part, hipStream_t s) {
+  const int P = rows > 0 ? (int)ppo_loss_partials(rows) : 0;  // rows = 0: the finish kernels alone, over no partials
+  const dim3 grid((unsigned)P), block(kPpoBlock), one(1), fin(2 * kAdvRuns);
+  if (P > 0) hipLaunchKernelGGL(adv_sum_kernel<0>, grid, block, 0, s, x, index, n_src, rows, out, part);
+  hipLaunchKernelGGL(adv_finish_kernel<0>, one, fin, 0, s, part, P, eps, out);
+  if (P > 0) hipLaunchKernelGGL(adv_sum_kernel<1>, grid, block, 0, s, x, index, n_src, rows, out, part);
+  hipLaunchKernelGGL(adv_finish_kernel<1>, one, fin, 0, s, part, P, eps, out);
+  return hipGetLastError();
 }
 
 long long ppo_loss_partials(long long rows) {

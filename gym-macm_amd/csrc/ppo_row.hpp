@@ -151,4 +151,21 @@ struct PpoGradArgs {
 hipError_t launch_mlp_ppo_grad(const MlpNet& net, const void* obs, bool obs_f64, long long rows, const PpoGradArgs& G,
                                float* grad, float* workspace, hipStream_t s);
 
+// What macm_ppo_grad_rows adds to that: position r of the call reads source row index[r] of obs and of G's
+// arrays, and the row's advantage is normalised as it is loaded. A position whose source row is outside
+// [0, n_src) is a tail lane: nothing of it is loaded.
+struct PpoRowsArgs {
+  const int32_t* index;  // [rows], or NULL: positions are rows (n_src is not read)
+  long long n_src;       // the source arrays' rows, at most 2^31 - 1
+  const double* norm;    // {mean, rstd}: adv = (float)(((double)adv - mean) rstd), or NULL
+};
+hipError_t launch_mlp_ppo_grad_rows(const MlpNet& net, const void* obs, bool obs_f64, long long rows,
+                                    const PpoGradArgs& G, const PpoRowsArgs& R, float* grad, float* workspace,
+                                    hipStream_t s);
+
+// macm_adv_moments (ppo_loss.hip): out = {mean, rstd, std, n} of x[index[r]] (index NULL: x[r]) over the
+// positions whose source row is in [0, n_src); part holds 2 doubles per block, ppo_loss_partials(rows) blocks
+hipError_t launch_adv_moments(const float* x, const int32_t* index, long long n_src, long long rows, double eps,
+                              double* out, double* part, hipStream_t s);
+
 }  // namespace macm

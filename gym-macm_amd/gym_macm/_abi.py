@@ -296,6 +296,10 @@ SIGNATURES = {
     "macm_ppo_loss": (c_int, [POINTER(MacmPpoConfig), c_int64] + [c_void_p] * 12 + [c_int64, c_void_p]),
     "macm_ppo_grad": (c_int, [POINTER(MacmPpoConfig), POINTER(MacmPolicyMlp), POINTER(MacmValueMlp), c_void_p, c_int32,
                               c_int64] + [c_void_p] * 9 + [c_int64, c_void_p]),
+    "macm_ppo_grad_rows": (c_int, [POINTER(MacmPpoConfig), POINTER(MacmPolicyMlp), POINTER(MacmValueMlp), c_void_p,
+                                   c_int32, c_int64, c_void_p, c_int64] + [c_void_p] * 10 + [c_int64, c_void_p]),
+    "macm_adv_moments": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p, c_void_p, c_int64,
+                                 c_void_p]),
     "macm_bots_flock": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
     "macm_bots_combat": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
 }

@@ -9,11 +9,19 @@ loss under torch.autograd, and the loss fused into the gradient launches.
     # or fused: neither the logits nor dL/dlogits exist in memory, one launch per net
     stats = ppo.ppo_grads(pol, crit, obs, actions, old_logp, adv, ret)   # accumulates into params.grad
     opt.step()
+    # epochs over shuffled minibatches with normalised advantages: nothing is gathered, nothing synchronises
+    for mb in ppo.minibatches(obs.numel() // 4, 32, device=obs.device):      # int32 index lists, block-shuffled
+        norm = ppo.adv_moments(adv, mb)                                    # float64 [4]: mean, rstd, std, n
+        ppo.ppo_grads(pol, crit, obs, actions, old_logp, adv, ret, index=mb, adv_norm=norm)
+        opt.step(); opt.zero_grad()
 
 ``stats`` is a float64 [8] device tensor: loss, policy_loss, value_loss, entropy, approx_kl, clip_frac,
 ratio_max, rows. In the first epoch, with ``old_logp`` from ``log_prob`` on the rollout's own logits, the
-ratio is exactly 1, approx_kl 0 and clip_frac 0. The means are over the rows of the call: a minibatch is a
-contiguous slice of the leading dimension, and advantage normalisation is the caller's.
+ratio is exactly 1, approx_kl 0 and clip_frac 0. The means are over the rows of the call. A minibatch of
+``ppo_grads`` is a contiguous slice of the leading dimension or, with ``index``, any list of rows
+(macm_ppo_grad_rows), and ``adv_norm`` normalises its advantages on the way in with the moments
+``adv_moments`` computed on the device. The autograd path (``ppo_loss`` with ``pol.forward``) keeps its
+contiguous rows: a user of that path gathers and normalises with torch as before.
 
 The per-row definition is float64 on the float32 inputs (include/macm.h). There is no CPU fallback.
 """
@@ -199,15 +207,95 @@ def ppo_loss(logits: torch.Tensor, values: torch.Tensor, actions: torch.Tensor, 
     return _PpoLoss.apply(logits, values, actions, old_logp, adv, ret, old_values, cfg)
 
 
+def _check_index(index, dev):
+    """index as the library takes it: int32, 1-D, contiguous, on dev (an int64 index is converted: a copy)."""
+    if index.dim() != 1 or index.dtype not in (torch.int32, torch.int64) or index.device != dev:
+        raise ValueError(f"index must be a 1-D int32 (or int64) tensor on {dev}")
+    return index.to(torch.int32).contiguous()
+
+
+def minibatches(n_rows: int, n_minibatches: int, generator: torch.Generator = None, block: int = 64,
+                device=None) -> list:
+    """n_minibatches int32 index tensors on `device` that together hold every row of range(n_rows) exactly
+    once: one epoch's minibatches for ``ppo_grads(index=...)`` and ``adv_moments``. The shuffle is over blocks of
+    `block` consecutive rows (aligned to multiples of block; a short last block leads the first minibatch) and
+    keeps the rows of a block in order; the minibatches' lengths differ by at most one block. block=1 is a full
+    shuffle of the rows.
+
+    Why 64 by default: 64 consecutive rows are one tile of the gradient kernel, and with 64 agents per env
+    they are one env's agents at one step, so the minibatches still mix steps and envs freely. A
+    block-shuffled gather loads whole cache lines; a row shuffle fetches a 128-byte line for each 16-byte
+    obs row (and for each 4-byte old_logp, adv and ret), which is what ``ppo_grads`` pays with block=1.
+    Plain torch: `generator` and `device` may be the CPU's."""
+    n_rows, m, block = int(n_rows), int(n_minibatches), int(block)
+    if n_rows < 0 or m < 1 or block < 1:
+        raise ValueError("minibatches: n_rows >= 0, n_minibatches >= 1 and block >= 1")
+    if n_rows >= 2 ** 31:
+        raise ValueError("minibatches: an int32 index names at most 2^31 - 1 rows")
+    n_blocks = -(-n_rows // block)
+    gdev = generator.device if generator is not None else torch.device("cpu")
+    order = torch.randperm(n_blocks, generator=generator, device=gdev)
+    if n_rows % block:  # the short block goes first, to a minibatch with the most blocks: lengths stay within a block
+        at = int((order == n_blocks - 1).nonzero()[0, 0])
+        order[at], order[0] = order[0].clone(), order[at].clone()
+    if device is not None:
+        order = order.to(device)
+    within = torch.arange(block, device=order.device)
+    out = []
+    for i in range(m):  # blocks i, i + m, i + 2 m, ... of the shuffled order: counts differ by at most one
+        rows = (order[i::m, None] * block + within[None, :]).reshape(-1)
+        out.append(rows[rows < n_rows].to(torch.int32))
+    return out
+
+
+def adv_moments(adv: torch.Tensor, index: torch.Tensor = None, eps: float = 1e-8) -> torch.Tensor:
+    """{mean, rstd, std, n} (a float64 [4] device tensor) of adv (float32, any shape, flattened) at the rows of
+    index (int32 1-D, None: all rows): the mean, 1 / (std + eps) with the unbiased std that ``tensor.std()``
+    gives, that std, and the number of positions whose index is inside adv (macm_adv_moments: two passes,
+    float64, deterministic). The result is what ``ppo_grads(adv_norm=...)`` takes, and nothing synchronises
+    in between. The workspace is this module's, as ppo_loss's is: calls belong on one stream."""
+    dev = adv.device
+    _check("adv", adv, dev, torch.float32, adv.shape)
+    if index is not None:
+        index = _check_index(index, dev)
+    if not 0 <= eps < float("inf"):
+        raise ValueError("eps must be finite and >= 0")
+    if dev.type != "cuda":
+        raise ValueError("adv_moments runs on a GPU device (no CPU fallback)")
+    rows = index.numel() if index is not None else adv.numel()
+    out = torch.empty((4,), dtype=torch.float64, device=dev)
+    ws = _workspace(None, rows, dev)
+    with torch.cuda.device(dev):
+        _abi.check(_abi.lib().macm_adv_moments(_p(adv), _p(index), adv.numel() if index is not None else 0, rows,
+                                               float(eps), _p(out), _p(ws), ws.numel(), _stream(adv)),
+                   "macm_adv_moments")
+    return out
+
+
 def ppo_grads(pol, crit, obs: torch.Tensor, actions: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor,
               ret: torch.Tensor, old_values: torch.Tensor = None, clip: float = 0.2, vf_coef: float = 0.5,
-              ent_coef: float = 0.01, vf_clip: float = None) -> torch.Tensor:
+              ent_coef: float = 0.01, vf_clip: float = None, index: torch.Tensor = None,
+              adv_norm: torch.Tensor = None) -> torch.Tensor:
     """stats (float64 [8]) of the clipped PPO loss of pol (an MlpPolicy) and crit (an MlpCritic) over obs
     [..., in_dim], with dL/dparams accumulated into pol.params.grad and crit.params.grad exactly as
     ``ppo_loss(pol.forward(obs), crit.forward(obs), ...)[0].backward()`` would, bit for bit, but with the loss
     inside the gradient launches (macm_ppo_grad): no logits, values or their gradients in memory. Either net
     may be None. The workspace is the first net's and grows on demand: calls on one object belong on one
-    stream."""
+    stream.
+
+    index (an int32 1-D device tensor, e.g. one of ``minibatches(...)``) makes the call a minibatch of those
+    rows (macm_ppo_grad_rows): obs and the per-row tensors are taken as [n_src, ...] with their leading
+    dimensions flattened, position r of the call reads row index[r] of each, and the means are over
+    len(index). The results have the bits of the call on ``index_select``-ed copies, which are never made. An
+    index outside [0, n_src) is skipped (it adds nothing and is never followed), where ``index_select`` would
+    fault. An int64 index is accepted and converted, which costs a copy per call. adv_norm (float64 [2] or [4]
+    on the device: mean and rstd, what ``adv_moments`` returns) normalises each advantage as it is loaded,
+    (adv - mean) * rstd in float64 rounded once to float32; it works without index too. Measured on the
+    flagship trajectory ("PPO over shuffled minibatches": an epoch of 32 minibatches of 2^20 rows):
+    23.2 ms with the block=64 index of ``minibatches`` against 22.6 ms for contiguous slices and 30.7 ms for
+    ``index_select`` copies; a full row shuffle (block=1) fetches a cache line per row and costs 24.6 ms, 6%
+    more than block=64 and still less than the copies. With both None the call is macm_ppo_grad exactly as
+    before. The autograd path (``ppo_loss``, ``pol.forward``) takes no index: gather with torch there."""
     if pol is None and crit is None:
         raise ValueError("pol and crit are both None")
     first = pol if pol is not None else crit
@@ -217,20 +305,31 @@ def ppo_grads(pol, crit, obs: torch.Tensor, actions: torch.Tensor, old_logp: tor
     first._check_rows(obs)
     dev, lead = first.device, tuple(obs.shape[:-1])
     _check_rows(dev, lead, actions, old_logp, adv, ret, old_values, pol is not None, crit is not None)
-    rows = obs.numel() // first.in_dim
+    n_src = rows = obs.numel() // first.in_dim
+    if index is not None:
+        index = _check_index(index, dev)
+        rows = index.numel()
+    if adv_norm is not None:
+        if adv_norm.device != dev or adv_norm.dtype != torch.float64 or adv_norm.dim() != 1 or \
+                adv_norm.numel() not in (2, 4) or not adv_norm.is_contiguous():
+            raise ValueError(f"adv_norm must be a contiguous float64 [2] or [4] tensor on {dev} (adv_moments' result)")
     cfg = config(clip, vf_coef, ent_coef, vf_clip)
     ws = _workspace(first, rows, dev)
     gp = torch.empty_like(pol.params, requires_grad=False) if pol is not None else None
     gv = torch.empty_like(crit.params, requires_grad=False) if crit is not None else None
     stats = torch.empty((8,), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _abi.check(_abi.lib().macm_ppo_grad(
-            ctypes.byref(cfg), ctypes.byref(pol.struct()) if pol is not None else None,
+    head = (ctypes.byref(cfg), ctypes.byref(pol.struct()) if pol is not None else None,
             ctypes.byref(crit.struct()) if crit is not None else None, _p(obs), 1 if obs.dtype == torch.float64 else 0,
-            rows, _p(actions) if pol is not None else None, _p(old_logp) if pol is not None else None,
+            rows)
+    tail = (_p(actions) if pol is not None else None, _p(old_logp) if pol is not None else None,
             _p(adv) if pol is not None else None, _p(ret) if crit is not None else None,
-            _p(old_values) if crit is not None else None, _p(gp), _p(gv), _p(stats), _p(ws), ws.numel(), _stream(obs)),
-            "macm_ppo_grad")
+            _p(old_values) if crit is not None else None, _p(gp), _p(gv), _p(stats), _p(ws), ws.numel(), _stream(obs))
+    with torch.cuda.device(dev):
+        if index is None and adv_norm is None:
+            _abi.check(_abi.lib().macm_ppo_grad(*head, *tail), "macm_ppo_grad")
+        else:
+            _abi.check(_abi.lib().macm_ppo_grad_rows(*head, _p(index), n_src, _p(adv_norm), *tail),
+                       "macm_ppo_grad_rows")
     for net, g in ((pol, gp), (crit, gv)):
         if net is not None:
             if net.params.grad is None:

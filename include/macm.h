@@ -722,6 +722,51 @@ int macm_ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const ma
                   const float* ret, const float* old_values, float* grad_policy, float* grad_value, double* stats,
                   void* workspace, int64_t workspace_bytes, void* stream);
 
+/*
+ * PPO updates over shuffled minibatches with normalised advantages: macm_ppo_grad reading its rows through
+ * an index list, and the moments of a minibatch's advantages from a deterministic device reduction.
+ *
+ * macm_ppo_grad_rows is macm_ppo_grad with three more arguments. Position r of the call, 0 <= r < rows,
+ * reads source row s = index[r] (int32 [rows]; index NULL: s = r) of obs, actions, old_logp, adv, ret and
+ * old_values, which hold n_src rows each; repeats and any order are allowed. With adv_norm (a DEVICE
+ * double[2] {mean, rstd}, read with no synchronise) the row's advantage is
+ *   (float)(((double)adv[s] - adv_norm[0]) * adv_norm[1])
+ * one subtraction and one multiplication in float64, one rounding to float32. Everything else is
+ * macm_ppo_grad's definition in terms of the position: k = 1 / rows, the means over rows, the tile and
+ * the wave of a position, the partials, the reductions and stats, so the association of every sum is a
+ * function of rows alone and never of the index values: the outputs have the bits of macm_ppo_grad
+ * called on contiguous gathered (and normalised) copies of the inputs. A position whose index is outside
+ * [0, n_src) is treated as a lane past rows: nothing of it is loaded, it adds exact zeros to the
+ * gradients and nothing to the stats, while k stays 1 / rows and stats[7] stays rows; no index value
+ * makes the library read outside the caller's arrays. With index NULL n_src is checked and not read.
+ * The workspace is macm_ppo_workspace(rows) bytes, rows being the index length.
+ * MACM_E_INVALID, with a message and nothing launched: everything macm_ppo_grad refuses; n_src < 0 or
+ * n_src > 2^31 - 1; index and adv_norm both NULL (that call is macm_ppo_grad: there is one way to do
+ * each thing); index not 4-byte or adv_norm not 8-byte aligned.
+ *
+ * macm_adv_moments: with x_r = (double)x[index ? index[r] : r] over the n positions whose source row
+ * is in [0, n_src) (index NULL: all rows of them; n_src is checked and not read),
+ *   mean = sum x_r / n (n = 0: 0); S2 = sum (x_r - mean)^2, a second pass with that mean
+ *   var = n > 1 ? S2 / (n - 1) : 0 (unbiased: torch's tensor.std()); std = sqrt(var); rstd = 1 / (std + eps)
+ *   out = {mean, rstd, std, (double)n}: a device double[4], and as it stands a valid adv_norm
+ * so that macm_ppo_grad_rows behind it computes (adv - mean) / (std + eps) of the minibatch with no
+ * synchronise between. The sums are float64 with no atomics: lane-local, a wave's lanes in lane order,
+ * the partials in a fixed order; their association is a function of rows alone, so the same arguments
+ * give the same bits on every call and stream. Four small launches ordered on `stream`. rows = 0
+ * writes {0, 1 / eps, 0, 0}. The workspace is the caller's as above; macm_ppo_workspace(rows) bytes
+ * suffice and are what is asked for. MACM_E_INVALID: x or out NULL, rows < 0, n_src outside
+ * [0, 2^31 - 1], eps negative or not finite, x or index not 4-byte, out not 8-byte aligned, workspace
+ * NULL, not 16-byte aligned or workspace_bytes too small while rows > 0. Additive: MACM_ABI_VERSION stays 9.
+ */
+int macm_ppo_grad_rows(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c, const void* obs,
+                       int32_t obs_f64, int64_t rows, const int32_t* index /* [rows] or NULL */, int64_t n_src,
+                       const double* adv_norm /* device {mean, rstd} or NULL */, const uint8_t* actions,
+                       const float* old_logp, const float* adv, const float* ret, const float* old_values,
+                       float* grad_policy, float* grad_value, double* stats, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+int macm_adv_moments(const float* x, const int32_t* index /* [rows] or NULL */, int64_t n_src, int64_t rows, double eps,
+                     double* out /* device double[4] */, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Observation of the current state without stepping (Flock.get_obs, mvmnt.py:181-222). */
 int macm_world_observe(macm_world* w, const macm_outputs* out, void* stream);
 

@@ -4,8 +4,9 @@
 #   tools/kernel_resources.sh <dir holding csrc/>   (diff two trees to see what a change costs)
 # The policy and critic kernels are among them: the ObsPol / ObsPolV instantiations of the two rollout
 # units, policy.hip's policy_flock_kernel, value_flock_kernel and gae_kernel, and policy_grad.hip's
-# mlp_grad_kernel and mlp_ppo_grad_kernel (one wave per block: waves per CU = 4 x waves/SIMD) and
-# mlp_grad_reduce_kernel, and ppo_loss.hip's policy_logp_kernel, ppo_loss_kernel and ppo_stats_kernel.
+# mlp_grad_kernel, mlp_ppo_grad_kernel and mlp_ppo_grad_rows_kernel (one wave per block: waves per CU =
+# 4 x waves/SIMD) and mlp_grad_reduce_kernel, and ppo_loss.hip's policy_logp_kernel, ppo_loss_kernel,
+# ppo_stats_kernel, adv_sum_kernel and adv_finish_kernel.
 cd $1
 for f in csrc/flock_step_w64.hip csrc/flock_rollout_w64.hip csrc/flock_rollout_ar_w64.hip csrc/flock_step_wg.hip csrc/tdm_step_wg.hip csrc/policy.hip csrc/policy_grad.hip csrc/ppo_loss.hip; do
   extra=""; case $f in csrc/flock_rollout_w64.hip|csrc/flock_rollout_ar_w64.hip) extra="-mllvm -disable-machine-licm";; esac
