@@ -176,12 +176,12 @@ int macm_ppo_loss(const macm_ppo_config* cfg, int64_t rows, const float* logits,
   return MACM_OK;
 }
 
-// macm_ppo_grad (R NULL) and macm_ppo_grad_rows (R: the index and the advantage's normalisation) behind
-// the latter's own checks
-static int ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c, const void* obs,
-                    int32_t obs_f64, int64_t rows, const PpoRowsArgs* R, const uint8_t* actions, const float* old_logp,
-                    const float* adv, const float* ret, const float* old_values, float* grad_policy,
-                    float* grad_value, double* stats, void* workspace, int64_t workspace_bytes, void* stream) {
+// What macm_ppo_grad, macm_ppo_grad_rows and macm_ppo_update refuse alike, before anything is launched
+static int ppo_grad_check(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c,
+                          const void* obs, int64_t rows, const uint8_t* actions, const float* old_logp,
+                          const float* adv, const float* ret, const float* old_values, const float* grad_policy,
+                          const float* grad_value, const double* stats, const void* workspace,
+                          int64_t workspace_bytes) {
   if (const int rc = ppo_check(cfg, rows, c && old_values, stats, workspace, workspace_bytes)) return rc;
   if (!p && !c) return fail(MACM_E_INVALID, "ppo: policy and critic are both NULL");
   if (p) {
@@ -199,7 +199,15 @@ static int ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const 
   for (const void* q : {(const void*)old_logp, (const void*)adv, (const void*)ret, (const void*)old_values,
                         (const void*)grad_policy, (const void*)grad_value})
     if (misaligned(q, 4)) return fail(MACM_E_INVALID, "ppo: the float32 arrays must be 4-byte aligned");
-  const hipStream_t s = (hipStream_t)stream;
+  return MACM_OK;
+}
+
+// macm_ppo_grad (R NULL) and macm_ppo_grad_rows (R: the index and the advantage's normalisation) behind
+// ppo_grad_check: the launches
+static int ppo_grad_launch(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c,
+                           const void* obs, int32_t obs_f64, int64_t rows, const PpoRowsArgs* R, const uint8_t* actions,
+                           const float* old_logp, const float* adv, const float* ret, const float* old_values,
+                           float* grad_policy, float* grad_value, double* stats, void* workspace, hipStream_t s) {
   if (rows == 0) {
     if (p) HIP_TRY(hipMemsetAsync(grad_policy, 0, sizeof(float) * net_of(p, kPolicyLogits).n_params(), s));
     if (c) HIP_TRY(hipMemsetAsync(grad_value, 0, sizeof(float) * net_of(c, 1).n_params(), s));
@@ -218,6 +226,17 @@ static int ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const 
   if (stats)
     HIP_TRY(launch_ppo_stats(part, (int)mlp_grad_partials(rows), rows, k, p != nullptr, c != nullptr, stats, s));
   return MACM_OK;
+}
+
+static int ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c, const void* obs,
+                    int32_t obs_f64, int64_t rows, const PpoRowsArgs* R, const uint8_t* actions, const float* old_logp,
+                    const float* adv, const float* ret, const float* old_values, float* grad_policy,
+                    float* grad_value, double* stats, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (const int rc = ppo_grad_check(cfg, p, c, obs, rows, actions, old_logp, adv, ret, old_values, grad_policy,
+                                    grad_value, stats, workspace, workspace_bytes))
+    return rc;
+  return ppo_grad_launch(cfg, p, c, obs, obs_f64, rows, R, actions, old_logp, adv, ret, old_values, grad_policy,
+                         grad_value, stats, workspace, (hipStream_t)stream);
 }
 
 int macm_ppo_grad(const macm_ppo_config* cfg, const macm_policy_mlp* p, const macm_value_mlp* c, const void* obs,
@@ -265,6 +284,167 @@ int macm_adv_moments(const float* x, const int32_t* index, int64_t n_src, int64_
     return fail(MACM_E_INVALID, "moments: workspace_bytes " + std::to_string(workspace_bytes) + " is below the " +
                                     std::to_string(ppo_workspace_bytes(rows)) + " of macm_ppo_workspace");
   HIP_TRY(launch_adv_moments(x, index, n_src, rows, eps, out, (double*)workspace, (hipStream_t)stream));
+  return MACM_OK;
+}
+
+// ---- the PPO update (ppo_adam.hip): the optimiser step, and minibatches enqueued in one call ---------------
+static int64_t adam_state_bytes(int n_p, int n_c) {
+  return (int64_t)kAdamHead * (int64_t)sizeof(double) + 2 * ((int64_t)n_p + n_c) * (int64_t)sizeof(float);
+}
+
+// The nets of a step: both checked, their parameter counts (an absent net: 0)
+static int adam_nets(const macm_policy_mlp* p, const macm_value_mlp* c, int* n_p, int* n_c) {
+  if (!p && !c) return fail(MACM_E_INVALID, "adam: policy and critic are both NULL");
+  if (p)
+    if (const int rc = mlp_check("policy", p)) return rc;
+  if (c)
+    if (const int rc = mlp_check("critic", c)) return rc;
+  *n_p = p ? net_of(p, kPolicyLogits).n_params() : 0;
+  *n_c = c ? net_of(c, 1).n_params() : 0;
+  return MACM_OK;
+}
+
+int macm_ppo_adam_state_bytes(const macm_policy_mlp* p, const macm_value_mlp* c, int64_t* bytes) {
+  if (!bytes) return fail(MACM_E_INVALID, "adam: bytes is NULL");
+  int n_p, n_c;
+  if (const int rc = adam_nets(p, c, &n_p, &n_c)) return rc;
+  *bytes = adam_state_bytes(n_p, n_c);
+  return MACM_OK;
+}
+
+// What macm_ppo_adam refuses, and macm_ppo_update with it; has_stats: the step will be given a stats row
+static int adam_check(const macm_adam_config* o, const macm_policy_mlp* p, const macm_value_mlp* c,
+                      const float* grad_policy, const float* grad_value, bool has_stats, const void* stats,
+                      const void* state, int64_t state_bytes) {
+  if (!o) return fail(MACM_E_INVALID, "adam: opt is NULL");
+  int n_p, n_c;
+  if (const int rc = adam_nets(p, c, &n_p, &n_c)) return rc;
+  for (int i = 0; i < 4; ++i)
+    if (o->reserved[i] != 0) return fail(MACM_E_INVALID, "adam: reserved must be 0");
+  if (!(o->lr >= 0.0) || std::isinf(o->lr)) return fail(MACM_E_INVALID, "adam: lr must be finite and >= 0");
+  if (!(o->beta1 >= 0.0 && o->beta1 < 1.0) || !(o->beta2 >= 0.0 && o->beta2 < 1.0))
+    return fail(MACM_E_INVALID, "adam: beta1 and beta2 must be in [0, 1)");
+  if (!(o->eps > 0.0) || std::isinf(o->eps)) return fail(MACM_E_INVALID, "adam: eps must be finite and > 0");
+  if (!(o->max_grad_norm >= 0.0) || std::isinf(o->max_grad_norm))
+    return fail(MACM_E_INVALID, "adam: max_grad_norm must be finite and >= 0 (0: no clipping)");
+  if (!(o->target_kl >= 0.0) || std::isinf(o->target_kl))
+    return fail(MACM_E_INVALID, "adam: target_kl must be finite and >= 0 (0: no gate)");
+  if (o->target_kl > 0.0 && (!has_stats || !p))
+    return fail(MACM_E_INVALID, "adam: target_kl > 0 needs stats and the policy (approx_kl is the policy's)");
+  if ((p && !grad_policy) || (c && !grad_value))
+    return fail(MACM_E_INVALID, "adam: grad_policy/grad_value is NULL for a net that is given");
+  if (!state) return fail(MACM_E_INVALID, "adam: state is NULL");
+  if (misaligned(grad_policy, 4) || misaligned(grad_value, 4))
+    return fail(MACM_E_INVALID, "adam: the gradients must be 4-byte aligned");
+  if (misaligned(stats, 8)) return fail(MACM_E_INVALID, "adam: stats must be 8-byte aligned");
+  if (misaligned(state, 8)) return fail(MACM_E_INVALID, "adam: state must be 8-byte aligned");
+  if (state_bytes < adam_state_bytes(n_p, n_c))
+    return fail(MACM_E_INVALID, "adam: state_bytes " + std::to_string(state_bytes) + " is below the " +
+                                    std::to_string(adam_state_bytes(n_p, n_c)) + " of macm_ppo_adam_state_bytes");
+  return MACM_OK;
+}
+
+// The step's arguments behind adam_check: the state's layout is the header's
+static AdamArgs adam_args(const macm_adam_config* o, const macm_policy_mlp* p, const macm_value_mlp* c,
+                          const float* grad_policy, const float* grad_value, const double* stats, void* state) {
+  const int n_p = p ? net_of(p, kPolicyLogits).n_params() : 0, n_c = c ? net_of(c, 1).n_params() : 0;
+  double* const head = (double*)state;
+  float* const mp = (float*)(head + kAdamHead);
+  float* const mc = mp + 2 * n_p;
+  AdamArgs A;
+  A.param[0] = p ? const_cast<float*>(p->params) : nullptr;  // (the structs declare what the forward reads; the step writes it)
+  A.param[1] = c ? const_cast<float*>(c->params) : nullptr;
+  A.grad[0] = grad_policy;
+  A.grad[1] = grad_value;
+  A.m[0] = mp;
+  A.v[0] = mp + n_p;
+  A.m[1] = mc;
+  A.v[1] = mc + n_c;
+  A.n[0] = n_p;
+  A.n[1] = n_c;
+  A.head = head;
+  A.stats = stats;
+  A.lr = o->lr;
+  A.beta1 = o->beta1;
+  A.beta2 = o->beta2;
+  A.omb1 = 1.0 - o->beta1;
+  A.omb2 = 1.0 - o->beta2;
+  A.eps = o->eps;
+  A.max_grad_norm = o->max_grad_norm;
+  A.target_kl = o->target_kl;
+  return A;
+}
+
+int macm_ppo_adam(const macm_adam_config* opt, const macm_policy_mlp* p, const macm_value_mlp* c,
+                  const float* grad_policy, const float* grad_value, const double* stats, void* state,
+                  int64_t state_bytes, void* stream) {
+  if (const int rc = adam_check(opt, p, c, grad_policy, grad_value, stats != nullptr, stats, state, state_bytes))
+    return rc;
+  HIP_TRY(launch_ppo_adam(adam_args(opt, p, c, grad_policy, grad_value, stats, state), (hipStream_t)stream));
+  return MACM_OK;
+}
+
+// The workspace of macm_ppo_update: macm_ppo_workspace(max_rows) (the moments' partials, then the gradient and
+// stat partials: the launches are ordered), and behind it the moments, a stats row and both gradients
+static int64_t update_fixed_bytes() {
+  return align16((4 + 8) * (int64_t)sizeof(double) + 2 * (int64_t)kGradMaxParams * (int64_t)sizeof(float));
+}
+
+int macm_ppo_update_workspace(int64_t max_rows, int64_t* bytes) {
+  if (!bytes) return fail(MACM_E_INVALID, "update: bytes is NULL");
+  if (max_rows < 0) return fail(MACM_E_INVALID, "update: max_rows must be >= 0");
+  *bytes = ppo_workspace_bytes(max_rows) + update_fixed_bytes();
+  return MACM_OK;
+}
+
+int macm_ppo_update(const macm_ppo_config* cfg, const macm_adam_config* opt, const macm_policy_mlp* p,
+                    const macm_value_mlp* c, const void* obs, int32_t obs_f64, int64_t n_src, const uint8_t* actions,
+                    const float* old_logp, const float* adv, const float* ret, const float* old_values,
+                    int32_t n_minibatches, const int32_t* const* index, const int64_t* rows, int32_t normalize_adv,
+                    double adv_eps, void* state, int64_t state_bytes, double* stats, void* workspace,
+                    int64_t workspace_bytes, void* stream) {
+  if (n_minibatches < 0) return fail(MACM_E_INVALID, "update: n_minibatches must be >= 0");
+  if (n_minibatches > 0 && (!index || !rows)) return fail(MACM_E_INVALID, "update: index/rows is NULL");
+  int64_t max_rows = 0;
+  for (int i = 0; i < n_minibatches; ++i) {
+    if (rows[i] < 0) return fail(MACM_E_INVALID, "update: rows[" + std::to_string(i) + "] must be >= 0");
+    if (rows[i] > 0 && !index[i]) return fail(MACM_E_INVALID, "update: index[" + std::to_string(i) + "] is NULL");
+    if (rows[i] > 0 && misaligned(index[i], 4))
+      return fail(MACM_E_INVALID, "update: index[" + std::to_string(i) + "] must be 4-byte aligned");
+    max_rows = std::max(max_rows, rows[i]);
+  }
+  if (const int rc = n_src_check(n_src)) return rc;
+  if (!(adv_eps >= 0.0) || std::isinf(adv_eps)) return fail(MACM_E_INVALID, "update: adv_eps must be finite and >= 0");
+  if (!workspace) return fail(MACM_E_INVALID, "update: workspace is NULL");
+  if (misaligned(workspace, 16)) return fail(MACM_E_INVALID, "update: workspace must be 16-byte aligned");
+  const int64_t need = ppo_workspace_bytes(max_rows) + update_fixed_bytes();
+  if (workspace_bytes < need)
+    return fail(MACM_E_INVALID, "update: workspace_bytes " + std::to_string(workspace_bytes) + " is below the " +
+                                    std::to_string(need) + " of macm_ppo_update_workspace");
+  char* const fixed = (char*)workspace + ppo_workspace_bytes(max_rows);
+  double* const norm = (double*)fixed;
+  double* const stat1 = norm + 4;
+  float* const gp = (float*)(stat1 + 8);
+  float* const gv = gp + kGradMaxParams;
+  if (const int rc = ppo_grad_check(cfg, p, c, obs, max_rows, actions, old_logp, adv, ret, old_values, gp, gv, stats,
+                                    workspace, workspace_bytes))
+    return rc;
+  if (const int rc = adam_check(opt, p, c, gp, gv, true, stats, state, state_bytes)) return rc;
+  const hipStream_t s = (hipStream_t)stream;
+  const bool moments = normalize_adv != 0 && p != nullptr;
+  for (int i = 0; i < n_minibatches; ++i) {
+    double* const st = stats ? stats + (size_t)i * 8 : stat1;
+    if (rows[i] == 0) {
+      if (stats) HIP_TRY(hipMemsetAsync(st, 0, 8 * sizeof(double), s));
+      continue;
+    }
+    if (moments) HIP_TRY(launch_adv_moments(adv, index[i], n_src, rows[i], adv_eps, norm, (double*)workspace, s));
+    const PpoRowsArgs R{index[i], n_src, moments ? norm : nullptr};
+    if (const int rc = ppo_grad_launch(cfg, p, c, obs, obs_f64, rows[i], &R, actions, old_logp, adv, ret, old_values,
+                                       gp, gv, st, workspace, s))
+      return rc;
+    HIP_TRY(launch_ppo_adam(adam_args(opt, p, c, gp, gv, st, state), s));
+  }
   return MACM_OK;
 }
 

@@ -168,4 +168,22 @@ hipError_t launch_mlp_ppo_grad_rows(const MlpNet& net, const void* obs, bool obs
 hipError_t launch_adv_moments(const float* x, const int32_t* index, long long n_src, long long rows, double eps,
                               double* out, double* part, hipStream_t s);
 
+// macm_ppo_adam (ppo_adam.hip): one workgroup of kAdamBlock threads steps both nets, [0] the policy and [1]
+// the critic; a net that is absent has n = 0 and its pointers are never followed. head is the state's
+// double[8] (include/macm.h), m and v the state's float32 moments
+constexpr int kAdamBlock = 256;
+constexpr int kAdamHead = 8;
+struct AdamArgs {
+  float* param[2];
+  const float* grad[2];
+  float* m[2];
+  float* v[2];
+  int n[2];
+  double* head;
+  const double* stats;  // [8] or NULL: stats[4] is approx_kl
+  double lr, beta1, beta2, omb1, omb2, eps;  // omb: 1 - beta, formed on the host
+  double max_grad_norm, target_kl;
+};
+hipError_t launch_ppo_adam(const AdamArgs& A, hipStream_t s);
+
 }  // namespace macm

@@ -103,6 +103,13 @@ class MacmPpoConfig(Structure):
                 ("reserved", c_int32 * 4)]
 
 
+class MacmAdamConfig(Structure):
+    """macm_adam_config: Adam's lr, betas and eps, the global-norm clip (0: none) and the KL gate (0: none),
+    by value on every call; reserved is 0."""
+    _fields_ = [("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double),
+                ("max_grad_norm", c_double), ("target_kl", c_double), ("reserved", c_int32 * 4)]
+
+
 class MacmState(Structure):
     _fields_ = [(n, c_void_p) for n in (
         "pos", "vel", "angle", "fat", "sleep", "targets", "contact_count", "contact_ab",
@@ -300,6 +307,14 @@ SIGNATURES = {
                                    c_int32, c_int64, c_void_p, c_int64] + [c_void_p] * 10 + [c_int64, c_void_p]),
     "macm_adv_moments": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p, c_void_p, c_int64,
                                  c_void_p]),
+    "macm_ppo_adam_state_bytes": (c_int, [POINTER(MacmPolicyMlp), POINTER(MacmValueMlp), POINTER(c_int64)]),
+    "macm_ppo_adam": (c_int, [POINTER(MacmAdamConfig), POINTER(MacmPolicyMlp), POINTER(MacmValueMlp), c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "macm_ppo_update_workspace": (c_int, [c_int64, POINTER(c_int64)]),
+    "macm_ppo_update": (c_int, [POINTER(MacmPpoConfig), POINTER(MacmAdamConfig), POINTER(MacmPolicyMlp),
+                                POINTER(MacmValueMlp), c_void_p, c_int32, c_int64] + [c_void_p] * 5 +
+                        [c_int32, POINTER(c_void_p), POINTER(c_int64), c_int32, c_double, c_void_p, c_int64, c_void_p,
+                         c_void_p, c_int64, c_void_p]),
     "macm_bots_flock": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
     "macm_bots_combat": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
 }

@@ -14,6 +14,11 @@ loss under torch.autograd, and the loss fused into the gradient launches.
         norm = ppo.adv_moments(adv, mb)                                    # float64 [4]: mean, rstd, std, n
         ppo.ppo_grads(pol, crit, obs, actions, old_logp, adv, ret, index=mb, adv_norm=norm)
         opt.step(); opt.zero_grad()
+    # the optimiser on the device too: Adam, the global-norm clip and a KL gate in one launch per step ...
+    opt = ppo.Adam(pol, crit, lr=3e-4, max_grad_norm=0.5, target_kl=0.03)   # opt.step(stats) in the loop above
+    # ... and the whole update (moments -> fused gradients -> step, per minibatch) as one call, no synchronise
+    epochs = [mb for _ in range(4) for mb in ppo.minibatches(obs.numel() // 4, 32, device=obs.device)]
+    stats = ppo.update(opt, obs, actions, old_logp, adv, ret, minibatches=epochs)     # float64 [128, 8]
 
 ``stats`` is a float64 [8] device tensor: loss, policy_loss, value_loss, entropy, approx_kl, clip_frac,
 ratio_max, rows. In the first epoch, with ``old_logp`` from ``log_prob`` on the rollout's own logits, the
@@ -336,4 +341,161 @@ def ppo_grads(pol, crit, obs: torch.Tensor, actions: torch.Tensor, old_logp: tor
                 net.params.grad = g
             else:
                 net.params.grad.add_(g)
+    return stats
+
+
+ADAM_HEAD = ("t", "beta1_pow", "beta2_pow", "stopped", "grad_norm", "clip_coef", "skipped_nonfinite", "reserved")
+
+
+class Adam:
+    """Adam over pol.params and crit.params (either net may be None) as one launch per step (macm_ppo_adam):
+    the global-norm clip of ``clip_grad_norm_`` (max_grad_norm, None: none), a KL gate (target_kl, None: none;
+    compared as given with ``stats[4]``: a user of the 1.5 x convention passes 1.5 x) and a guard that skips
+    a step whose gradient norm is not finite, all inside it. The definition is include/macm.h's: float64
+    arithmetic on float32 params, gradients and moments, checked bit for bit.
+
+    ``state`` is a zero-filled uint8 device tensor in the header's layout: eight doubles (``ADAM_HEAD``), then
+    m and v of the policy, then of the critic (float32). ``lr`` is a plain attribute, read at every step: a
+    schedule assigns to it. Once the gate has stopped the optimiser (approx_kl above target_kl, or NaN) every
+    later step is a no-op until ``resume()``. Calls on one object belong on one stream."""
+
+    def __init__(self, pol, crit, lr: float = 3e-4, betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm: float = None, target_kl: float = None):
+        inf = float("inf")
+        if not 0 <= lr < inf:
+            raise ValueError("lr must be finite and >= 0")
+        if len(betas) != 2 or not all(0 <= b < 1 for b in betas):
+            raise ValueError("betas must be two values in [0, 1)")
+        if not 0 < eps < inf:
+            raise ValueError("eps must be finite and > 0")
+        if max_grad_norm is not None and not 0 <= max_grad_norm < inf:
+            raise ValueError("max_grad_norm must be finite and >= 0 (None or 0: no clipping)")
+        if target_kl is not None and not 0 <= target_kl < inf:
+            raise ValueError("target_kl must be finite and >= 0 (None or 0: no gate)")
+        if pol is None and crit is None:
+            raise ValueError("pol and crit are both None")
+        if target_kl and pol is None:
+            raise ValueError("target_kl needs the policy (approx_kl is the policy's)")
+        first = pol if pol is not None else crit
+        if pol is not None and crit is not None and pol.device != crit.device:
+            raise ValueError("the policy and the critic must share a device")
+        self.pol, self.crit, self.device = pol, crit, first.device
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.max_grad_norm = 0.0 if max_grad_norm is None else float(max_grad_norm)
+        self.target_kl = 0.0 if target_kl is None else float(target_kl)
+        n = ctypes.c_int64(0)
+        _abi.check(_abi.lib().macm_ppo_adam_state_bytes(self._net(pol), self._net(crit), ctypes.byref(n)),
+                   "macm_ppo_adam_state_bytes")
+        self.state = torch.zeros((int(n.value),), dtype=torch.uint8, device=self.device)
+        self._ws = None  # update()'s workspace, grown on demand
+
+    @staticmethod
+    def _net(net):
+        return ctypes.byref(net.struct()) if net is not None else None
+
+    def config(self):
+        """The macm_adam_config of the hyperparameters as they stand."""
+        return _abi.MacmAdamConfig(self.lr, self.betas[0], self.betas[1], self.eps, self.max_grad_norm, self.target_kl,
+                                   (ctypes.c_int32 * 4)(0, 0, 0, 0))
+
+    def step(self, stats: torch.Tensor = None):
+        """One step from pol.params.grad and crit.params.grad, which ``ppo_grads`` or ``loss.backward()`` left
+        there; stats (float64 [8], what ``ppo_grads`` returned) feeds the KL gate and is needed with target_kl."""
+        grads = []
+        for net, what in ((self.pol, "pol"), (self.crit, "crit")):
+            g = net.params.grad if net is not None else None
+            if net is not None:
+                if g is None:
+                    raise ValueError(f"{what}.params.grad is None: nothing to step from")
+                _check(f"{what}.params.grad", g, self.device, torch.float32, net.params.shape)
+            grads.append(g)
+        if stats is not None:
+            _check("stats", stats, self.device, torch.float64, (8,))
+        elif self.target_kl > 0:
+            raise ValueError("target_kl needs the stats of the gradient call")
+        cfg = self.config()
+        with torch.cuda.device(self.device):
+            _abi.check(_abi.lib().macm_ppo_adam(ctypes.byref(cfg), self._net(self.pol), self._net(self.crit),
+                                                _p(grads[0]), _p(grads[1]), _p(stats), _p(self.state),
+                                                self.state.numel(), _stream(self.state)), "macm_ppo_adam")
+
+    def zero_grad(self):
+        """Drops both nets' .grad (as torch's zero_grad(set_to_none=True)): the next ``ppo_grads`` sets it."""
+        for net in (self.pol, self.crit):
+            if net is not None:
+                net.params.grad = None
+
+    def head(self) -> torch.Tensor:
+        """The state's eight doubles (ADAM_HEAD) as a float64 [8] device view: no copy, no synchronise."""
+        return self.state[:64].view(torch.float64)
+
+    def moments(self, which: str):
+        """(m, v) of "pol" or "crit": float32 views into the state."""
+        n_p = self.pol.params.numel() if self.pol is not None else 0
+        n_c = self.crit.params.numel() if self.crit is not None else 0
+        f = self.state[64:].view(torch.float32)
+        at, n = (0, n_p) if which == "pol" else (2 * n_p, n_c)
+        return f[at:at + n], f[at + n:at + 2 * n]
+
+    def resume(self):
+        """Clears the stopped word with a fill on the current stream: the steps behind it apply again."""
+        self.head()[3:4].zero_()
+
+    def info(self) -> dict:
+        """The head as a dict of Python floats. This copies to the host: it synchronises the stream."""
+        return dict(zip(ADAM_HEAD, self.head().cpu().tolist()))
+
+
+def update_workspace_bytes(max_rows: int) -> int:
+    n = ctypes.c_int64(0)
+    _abi.check(_abi.lib().macm_ppo_update_workspace(int(max_rows), ctypes.byref(n)), "macm_ppo_update_workspace")
+    return int(n.value)
+
+
+def update(opt: Adam, obs: torch.Tensor, actions: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor,
+           ret: torch.Tensor, old_values: torch.Tensor = None, minibatches=(), normalize_adv: bool = True,
+           adv_eps: float = 1e-8, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.01,
+           vf_clip: float = None, out: torch.Tensor = None) -> torch.Tensor:
+    """stats (float64 [len(minibatches), 8], STATS per row; `out` if given) of a whole PPO update in one call (macm_ppo_update):
+    for each index tensor of `minibatches` (int32 1-D device tensors, e.g. the lists of ``minibatches(...)`` of
+    one epoch or of several, one after the other) the moments of its advantages (normalize_adv), the fused
+    gradients of opt's nets at those rows and opt's step, gated by that minibatch's approx_kl, all enqueued on
+    the current stream with nothing synchronising in between. The params, opt.state and the stats have the
+    bits of the loop ``adv_moments -> ppo_grads(index=, adv_norm=) -> opt.step(stats) -> opt.zero_grad()``.
+    ``.grad`` is not touched: the gradients live in opt's workspace, which grows on demand.
+
+    An empty minibatch is skipped whole (a zero stats row, no step). After a KL stop the remaining minibatches'
+    gradients are still computed and their stats rows written (they describe the unchanged params): ending
+    early on the host would need a synchronise per minibatch. ``opt.head()`` tells afterwards, on the device,
+    whether and ``opt.info()`` (which synchronises) how it ended."""
+    if not isinstance(opt, Adam):
+        raise ValueError("opt must be a gym_macm.ppo.Adam")
+    pol, crit = opt.pol, opt.crit
+    first = pol if pol is not None else crit
+    if pol is not None and crit is not None and pol.in_dim != crit.in_dim:
+        raise ValueError("the policy and the critic must share in_dim (they read the same obs rows)")
+    _check_cfg(clip, vf_coef, ent_coef, vf_clip, old_values if crit is not None else None)
+    first._check_rows(obs)
+    dev, lead = first.device, tuple(obs.shape[:-1])
+    _check_rows(dev, lead, actions, old_logp, adv, ret, old_values, pol is not None, crit is not None)
+    if not 0 <= adv_eps < float("inf"):
+        raise ValueError("adv_eps must be finite and >= 0")
+    index = [_check_index(mb, dev) for mb in minibatches]
+    n_mb, n_src = len(index), obs.numel() // first.in_dim
+    need = update_workspace_bytes(max([mb.numel() for mb in index], default=0))
+    if opt._ws is None or opt._ws.numel() < need:
+        opt._ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    stats = out if out is not None else torch.empty((n_mb, 8), dtype=torch.float64, device=dev)
+    _check("out", stats, dev, torch.float64, (n_mb, 8))
+    ptrs = (ctypes.c_void_p * max(n_mb, 1))(*[mb.data_ptr() for mb in index])
+    rows = (ctypes.c_int64 * max(n_mb, 1))(*[mb.numel() for mb in index])
+    cfg, acfg = config(clip, vf_coef, ent_coef, vf_clip), opt.config()
+    with torch.cuda.device(dev):
+        _abi.check(_abi.lib().macm_ppo_update(
+            ctypes.byref(cfg), ctypes.byref(acfg), Adam._net(pol), Adam._net(crit), _p(obs),
+            1 if obs.dtype == torch.float64 else 0, n_src, _p(actions) if pol is not None else None,
+            _p(old_logp) if pol is not None else None, _p(adv) if pol is not None else None,
+            _p(ret) if crit is not None else None, _p(old_values) if crit is not None else None, n_mb, ptrs, rows,
+            1 if normalize_adv else 0, float(adv_eps), _p(opt.state), opt.state.numel(), _p(stats), _p(opt._ws),
+            opt._ws.numel(), _stream(obs)), "macm_ppo_update")
     return stats

@@ -767,6 +767,96 @@ int macm_ppo_grad_rows(const macm_ppo_config* cfg, const macm_policy_mlp* p, con
 int macm_adv_moments(const float* x, const int32_t* index /* [rows] or NULL */, int64_t n_src, int64_t rows, double eps,
                      double* out /* device double[4] */, void* workspace, int64_t workspace_bytes, void* stream);
 
+/*
+ * The PPO update on device: Adam with global-norm clipping, a KL gate and a non-finite guard in one launch
+ * (macm_ppo_adam), and any number of minibatches (moments -> fused gradients -> step) enqueued by one call
+ * with nothing synchronising (macm_ppo_update).
+ *
+ * macm_ppo_adam updates the params of both nets in place from grad_policy [n_p] and grad_value [n_c] (n_p,
+ * n_c: the nets' parameter counts, at most 1,577 each; a net that is NULL has n = 0). One workgroup of 256
+ * threads; the elements are the concatenation policy then critic, j = 0 .. n_p + n_c - 1, and element j
+ * belongs to thread j mod 256. All arithmetic is float64 on the float32 inputs, every operation rounded
+ * once, in the association written here, with + - * / sqrt only; what is stored as float32 is one rounding
+ * of a float64.
+ *
+ * state is device memory, 8-byte aligned, macm_ppo_adam_state_bytes(p, c) = 64 + 8 (n_p + n_c) bytes:
+ *   double head[8]; float m_p[n_p]; float v_p[n_p]; float m_c[n_c]; float v_c[n_c]
+ *   head[0] t, the steps applied         head[4] the last gradient norm
+ *   head[1] beta1^t                      head[5] the last clip coefficient
+ *   head[2] beta2^t                      head[6] the steps skipped for a non-finite norm
+ *   head[3] stopped, 0 or 1              head[7] 0
+ * An all-zero state is a fresh optimiser: with t = 0 both powers are taken as 1. The powers are running
+ * products (p1' = p1 beta1), never a pow. The state belongs to one pair of net shapes.
+ *
+ * One call, in this order:
+ *   1. head[3] != 0: nothing is written at all (a stopped optimiser stays as it is until the caller
+ *      writes 0.0 to head[3]).
+ *   2. stats given and target_kl > 0 and !(stats[4] <= target_kl): head[3] = 1, nothing else is written.
+ *      stats[4] is approx_kl of macm_ppo_grad's stats; a NaN stops.
+ *   3. s_i (thread i) = the sum over its elements j = i, i + 256, ... in ascending j, from 0, of
+ *      (double)g_j (double)g_j; then s[i] += s[i + d] for i < d, d = 128, 64, ..., 1; norm = sqrt(s[0]).
+ *      norm not finite: head[6] += 1, head[4] = norm, nothing else is written.
+ *   4. coef = max_grad_norm > 0 ? min(1, max_grad_norm / (norm + 1e-6)) : 1    (torch's clip_grad_norm_)
+ *   5. p1 = t == 0 ? 1 : head[1]; p2 likewise; p1' = p1 beta1; p2' = p2 beta2; per element
+ *        g = (double)grad coef
+ *        m' = (float)(beta1 (double)m + (1 - beta1) g)
+ *        v' = (float)(beta2 (double)v + (1 - beta2) (g g))
+ *        param' = (float)((double)param - lr (((double)m' / (1 - p1')) / (sqrt((double)v' / (1 - p2')) + eps)))
+ *      with 1 - beta formed on the host in double.
+ *   6. head[0] = t + 1, head[1] = p1', head[2] = p2', head[4] = norm, head[5] = coef.
+ * The config is passed by value on every call: a schedule is the caller changing lr. The params are written
+ * in place, and the next launch on the stream reads them from memory: stream order is the only ordering
+ * needed. The gradients are not modified. (macm_policy_mlp and macm_value_mlp declare params const because
+ * every other call only reads them; this one writes through that pointer, so the memory must be writable.)
+ * MACM_E_INVALID, with a message and nothing launched: opt NULL, both nets NULL, a net outside the supported
+ * shapes, a gradient NULL for a net that is given, state NULL, a misaligned pointer (gradients 4 bytes, stats
+ * and state 8), state_bytes below macm_ppo_adam_state_bytes, reserved != 0, lr negative or not finite, a beta
+ * outside [0, 1), eps <= 0 or not finite, max_grad_norm or target_kl negative or not finite, target_kl > 0
+ * without stats or without the policy.
+ *
+ * macm_ppo_update is a host loop over the launches of macm_adv_moments, macm_ppo_grad_rows and
+ * macm_ppo_adam: for minibatch i = 0 .. n_minibatches - 1, with index[i] (a device int32 [rows[i]]; index
+ * and rows themselves are HOST arrays) naming source rows of the n_src-row arrays,
+ *   the moments of adv at index[i] (if normalize_adv and the policy is given; eps = adv_eps),
+ *   the fused gradient launch of each net that is given, with those moments as adv_norm,
+ *   the statistics into stats[8 i .. 8 i + 7] (stats: device double [n_minibatches, 8], or NULL),
+ *   the step, gated by that row of statistics,
+ * all on `stream`, nothing synchronised, nothing allocated; the moments, the gradients and (stats NULL) the
+ * statistics live in the workspace and are reused from minibatch to minibatch, the launches being ordered.
+ * The results have the bits of the same sequence of single calls. A minibatch of 0 rows is skipped whole:
+ * its stats row is zeroed and no step is taken (a zero gradient would still move the params on momentum).
+ * After a KL stop the remaining minibatches' gradient launches still run and their stats rows are written;
+ * they describe the unchanged params. That waste is bounded by the call; ending early on the host would
+ * need the very synchronise this entry point exists to avoid. Epochs are the caller's notion: two epochs
+ * are the two epochs' minibatches in one list. The workspace is the caller's, device memory, 16-byte
+ * aligned, macm_ppo_update_workspace(max_rows) bytes for the largest rows[i] (nondecreasing in max_rows).
+ * MACM_E_INVALID, with a message and nothing launched: everything macm_ppo_grad_rows and macm_ppo_adam
+ * refuse, n_minibatches < 0, index or rows NULL while n_minibatches > 0, a rows[i] < 0, an index[i] NULL or
+ * misaligned while rows[i] > 0, adv_eps negative or not finite, workspace NULL or too small.
+ * Additive: no struct changed, MACM_ABI_VERSION stays 9.
+ */
+typedef struct macm_adam_config {
+  double lr, beta1, beta2, eps;   /* by value on every call: a schedule is the caller changing lr */
+  double max_grad_norm;           /* 0: no clipping */
+  double target_kl;               /* 0: no gate; compared as given with stats[4] (a user of the 1.5 x convention passes 1.5 x) */
+  int32_t reserved[4];            /* 0 */
+} macm_adam_config;
+
+int macm_ppo_adam_state_bytes(const macm_policy_mlp* p, const macm_value_mlp* c, int64_t* bytes);
+int macm_ppo_adam(const macm_adam_config* opt, const macm_policy_mlp* p, const macm_value_mlp* c,
+                  const float* grad_policy, const float* grad_value, const double* stats /* [8] or NULL */,
+                  void* state, int64_t state_bytes, void* stream);
+
+int macm_ppo_update_workspace(int64_t max_rows, int64_t* bytes);
+int macm_ppo_update(const macm_ppo_config* cfg, const macm_adam_config* opt,
+                    const macm_policy_mlp* p, const macm_value_mlp* c, const void* obs, int32_t obs_f64, int64_t n_src,
+                    const uint8_t* actions, const float* old_logp, const float* adv, const float* ret,
+                    const float* old_values, int32_t n_minibatches,
+                    const int32_t* const* index /* host array of device pointers */,
+                    const int64_t* rows /* host array */, int32_t normalize_adv, double adv_eps,
+                    void* state, int64_t state_bytes, double* stats /* device [n_minibatches, 8] or NULL */,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Observation of the current state without stepping (Flock.get_obs, mvmnt.py:181-222). */
 int macm_world_observe(macm_world* w, const macm_outputs* out, void* stream);
 
