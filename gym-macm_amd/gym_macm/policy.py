@@ -22,7 +22,14 @@ and ``gae`` turns a trajectory into advantages and returns in one launch:
     vals = torch.empty((K + 1, E, N), device=dev); vals[0] = crit.value(vec.obs)
     boot = torch.empty((K, E, N), device=dev)
     traj = vec.rollout_policy(acts, K, noise=g, trajectory=True, logits=lg, values=vals, boot=boot)
-    adv, ret = gae(traj["reward"], vals[:K], boot, traj["done"], 0.99, 0.95)
+    t = ppo.transitions(traj, acts, lg, vals, boot)   # gym_macm.ppo: each decision beside its own step, as views
+    adv, ret = gae(t["reward"], t["values"], t["boot"], t["done"], 0.99, 0.95)
+
+The launch's rows are staggered: step k executes action row k and writes reward, done, boot and obs row k; the
+decision taken from obs row k goes to action row k + 1, with its logits in logits row k and the value of the obs
+it saw in values row k + 1. ``values[:K]`` therefore belongs to the decisions of action rows 0 .. K-1, each taken
+from the obs before its step, and ``transitions`` pairs obs[j], logits[j] with acts[j + 1], vals[j + 1],
+reward[j + 1], done[j + 1] and boot[j + 1] for the K - 1 decisions the launch both took and stepped.
 
 Learning on those rows stays in the library too: ``forward`` is the same kernel under torch.autograd,
 and its backward is one launch per net (macm_policy_grad / macm_value_grad), with no nn.Module copy
@@ -30,9 +37,9 @@ of the net and no per-row activation kept:
 
     pol.params.requires_grad_(True); crit.params.requires_grad_(True)
     opt = torch.optim.Adam([pol.params, crit.params], lr=3e-4)
-    lg = pol.forward(traj["obs"])          # [..., 9], the bits rollout_policy stored at these params
-    v = crit.forward(traj["obs"])          # [...]
-    loss = ppo_loss(lg, old_logits, actions, adv, ret, v)   # the caller's torch code, any loss
+    lg = pol.forward(t["obs"])             # [..., 9], the bits rollout_policy stored at these params
+    v = crit.forward(t["obs"])             # [...]
+    loss = ppo_loss(lg, t["logits"], t["actions"], adv, ret, v)   # the caller's torch code, any loss
     loss.backward(); opt.step()            # params change in place: the next launch reads them
 
 The clipped PPO loss itself on the device, composed with ``forward`` or fused into the gradient launches,
@@ -264,9 +271,12 @@ class MlpCritic(_Mlp):
 def gae(reward: torch.Tensor, values: torch.Tensor, boot: torch.Tensor, done: torch.Tensor, gamma: float, lam: float,
         adv: torch.Tensor = None, ret: torch.Tensor = None):
     """(adv, ret), float32 [K, E, N]: generalised advantage estimation over a trajectory in one launch
-    (macm_gae). reward, values and boot are float32 [K, E, N] (values: the first K rows of the launch's
-    [K + 1, E, N] buffer), done uint8 [K, E]; boot[k] is V of the observation step k produced, so every
-    end bootstraps from its own terminal observation, and a done row cuts the recursion."""
+    (macm_gae). reward, values and boot are float32 [K, E, N], done uint8 [K, E]; values[k] is V of the
+    observation the action of step k was taken from and boot[k] V of the observation step k produced, so
+    every end bootstraps from its own terminal observation, and a done row cuts the recursion. adv[k] is the
+    advantage of the action step k executed. On the rows of ``gym_macm.ppo.transitions`` that action is the
+    row's own; on a launch's raw buffers (values: the first K rows of its [K + 1, E, N] buffer) it is action
+    row k, taken from the obs before step k, not from obs row k."""
     dev = reward.device
     if reward.dim() != 3:
         raise ValueError("reward must be a [K, E, N] tensor")

@@ -1,7 +1,11 @@
 """The clipped PPO loss on device (include/macm.h, macm_ppo_loss): log-probabilities from stored logits, the
 loss under torch.autograd, and the loss fused into the gradient launches.
 
-    old_logp = ppo.log_prob(lg, traj_actions)              # once, from the logits rollout_policy stored
+    # the rows of a trajectory launch, each decision beside its own reward: views, nothing copied or launched
+    t = ppo.transitions(traj, acts, lg, vals, boot)        # row j: obs[j], logits[j] -> acts[j + 1], reward[j + 1]
+    adv, ret = gae(t["reward"], t["values"], t["boot"], t["done"], 0.99, 0.95)
+    obs, actions, old_values = t["obs"], t["actions"], t["values"]
+    old_logp = ppo.log_prob(t["logits"], actions)          # once, from the logits rollout_policy stored
     pol.params.requires_grad_(True); crit.params.requires_grad_(True)
     # composed with the forward kernels: logits and dL/dlogits exist, nothing else per row is kept
     loss, stats = ppo.ppo_loss(pol.forward(obs), crit.forward(obs), actions, old_logp, adv, ret)
@@ -107,6 +111,56 @@ def _check_cfg(clip, vf_coef, ent_coef, vf_clip, old_values):
         raise ValueError("old_values needs vf_clip > 0")
     if old_values is None and vf_clip is not None:
         raise ValueError("vf_clip needs old_values")
+
+
+def transitions(traj: dict, actions: torch.Tensor, logits: torch.Tensor, values: torch.Tensor,
+                boot: torch.Tensor) -> dict:
+    """The aligned rows of one trajectory launch of ``rollout_policy(..., trajectory=True, logits=, values=,
+    boot=)``: a dict of obs, actions, logits, values, reward, done and boot whose row j holds one decision and
+    what came of it, for the K - 1 decisions j = 0 .. K-2 that the launch both took and stepped.
+
+    The launch's buffers are staggered (include/macm.h): step k executes action row k and writes reward[k],
+    done[k], boot[k] and obs row k; the decision taken from obs row k, with noise row k, leaves its logits in
+    logits row k, its action in actions row k + 1 and the value of the obs it saw in values row k + 1, and step
+    k + 1 executes it. So decision j is
+
+        obs[j], logits[j]  ->  actions[j + 1], values[j + 1]  ->  reward[j + 1], done[j + 1], boot[j + 1]
+
+    and the result is ``traj["obs"][:K-1]``, ``actions[1:K]``, ``logits[:K-1]``, ``values[1:K]``,
+    ``traj["reward"][1:]``, ``traj["done"][1:]`` and ``boot[1:]``: leading-dimension slices, so every entry is a
+    contiguous view of its buffer. Nothing is copied, gathered or launched. ``gae`` on the result's reward,
+    values, boot and done gives the advantage and return of each row's own action; ``log_prob`` on its logits
+    and actions gives the old log-probabilities (the ratio of the first epoch is then exactly 1).
+
+    Two decisions per launch are not among the rows. The decision of action row 0 is the caller's: it was taken
+    before the launch (``pol.act(vec.obs)``), and its logits and its obs are not in the launch's buffers. The
+    decision of action row K (from obs row K - 1, logits row K - 1) is taken by this launch but stepped by the
+    next one, whose action row 0 it is: its reward is not known yet.
+
+    traj holds obs [K, E, N, OD], reward [K, E, N] and done [K, E]; actions is [K + 1, E, N, 3], logits
+    [K, E, N, 9], values [K + 1, E, N] and boot [K, E, N]. ValueError: leading sizes that do not agree on one K,
+    K < 2, a tensor that is not contiguous, or the overwrite form's shapes ([E, N, ...] with no step dimension)."""
+    for f in ("obs", "reward", "done"):
+        if traj.get(f) is None:
+            raise ValueError(f"traj must hold obs, reward and done: {f} is missing")
+    reward = traj["reward"]
+    if reward.dim() != 3:
+        raise ValueError("traj['reward'] must be [K, E, N]: the trajectory form (the overwrite form keeps no rows)")
+    K, E, N = (int(d) for d in reward.shape)
+    want = (("obs", traj["obs"], (K, E, N, None)), ("reward", reward, (K, E, N)), ("done", traj["done"], (K, E)),
+            ("actions", actions, (K + 1, E, N, 3)), ("logits", logits, (K, E, N, N_LOGITS)),
+            ("values", values, (K + 1, E, N)), ("boot", boot, (K, E, N)))
+    for name, t, shape in want:
+        if t.dim() != len(shape) or any(s is not None and int(d) != s for d, s in zip(t.shape, shape)):
+            raise ValueError(f"{name} is {list(t.shape)}: with reward [{K}, {E}, {N}] the trajectory form is "
+                             f"{[s if s is not None else 'OD' for s in shape]} (obs, reward, done, logits and boot "
+                             "have K rows, actions and values K + 1)")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous: the rows are views of the launch's buffers")
+    if K < 2:
+        raise ValueError(f"K = {K}: a launch of fewer than 2 steps both takes and steps no decision")
+    return dict(obs=traj["obs"][:K - 1], actions=actions[1:K], logits=logits[:K - 1], values=values[1:K],
+                reward=reward[1:], done=traj["done"][1:], boot=boot[1:])
 
 
 def log_prob(logits: torch.Tensor, actions: torch.Tensor, entropy: torch.Tensor = None) -> torch.Tensor:

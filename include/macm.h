@@ -598,7 +598,12 @@ int macm_world_rollout_policy_value_traj(macm_world* w, uint8_t* actions, int32_
 /*
  * Generalised advantage estimation over a trajectory, any env kind, all float32. reward, values, boot,
  * adv and ret are [n_steps, E, N] (values may point at the first n_steps rows of the launch's
- * [n_steps + 1, E, N] buffer); done is [n_steps, E], any nonzero byte counts as done. With
+ * [n_steps + 1, E, N] buffer); done is [n_steps, E], any nonzero byte counts as done. values[k] is V of
+ * the observation the action of step k was taken from, so adv[k] and ret[k] belong to action row k of
+ * macm_world_rollout_policy_value_traj, the decision taken from obs row k - 1 (logits row k - 1), and
+ * values[:n_steps] to the decisions of action rows 0 .. n_steps - 1: not to obs row k, which step k
+ * wrote. A learner pairs obs[j], logits[j], actions[j + 1] and values[j + 1] with reward[j + 1],
+ * done[j + 1] and boot[j + 1] (all leading-dimension slices of the buffers) and runs this on those. With
  * gl = gamma * lambda (one float32 multiply) and carry = +0.0f, for k from n_steps - 1 down to 0:
  *   delta  = fmaf(gamma, boot[k], reward[k]) - values[k]      one fma, one subtraction
  *   adv[k] = done[k, e] ? delta : fmaf(gl, carry, delta)

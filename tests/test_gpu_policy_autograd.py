@@ -1,5 +1,6 @@
 """MlpPolicy.forward / MlpCritic.forward under torch.autograd, on a small trajectory of the closed loop (4 envs
-of 8 agents, 3 steps, autoreset on with every episode ending at its 2nd step): the forward has the bits the
+of 8 agents, the 3 aligned decisions of a 4-step launch (gym_macm.ppo.transitions), autoreset on with every
+episode ending at its 2nd step): the forward has the bits the
 launch stored; the backward of a PPO-shaped torch loss gives params.grad within grad_ref.tol of the reference
 fed with the loss's own dL/dlogits (dL/dvalue), and the bits of a direct macm_policy_grad (macm_value_grad)
 call; two backward passes accumulate; after an optimizer step the next launch reads the new params with no
@@ -16,6 +17,7 @@ import policy_ref as pr
 pytestmark = pytest.mark.gpu
 
 from gym_macm import _abi  # noqa: E402
+from gym_macm import ppo  # noqa: E402
 from gym_macm.policy import MlpCritic, MlpPolicy, gae  # noqa: E402
 from gym_macm.vec import FlockVec  # noqa: E402
 
@@ -49,18 +51,22 @@ def collect(H, nh, seed=37):
 
 
 def launch(c):
+    """A launch of K + 1 steps and its K aligned decisions (ppo.transitions): obs, logits, adv and ret are the
+    decisions' rows; acts, vals, boot and done are the launch's own rows, cut to the steps the decisions saw."""
     vec, pol, crit = c["vec"], c["pol"], c["crit"]
+    L = K + 1
     f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=DEV)
-    acts = torch.empty((K + 1, E, N, 3), dtype=torch.uint8, device=DEV)
+    acts = torch.empty((L + 1, E, N, 3), dtype=torch.uint8, device=DEV)
     pol.act(vec.obs, out=acts[0])
-    noise = torch.from_numpy(pr.gumbel_noise((K, E, N, 9), 5)).to(DEV)
-    lg, vals, boot = f32(K, E, N, 9), f32(K + 1, E, N), f32(K, E, N)
+    noise = torch.from_numpy(np.concatenate([pr.gumbel_noise((K, E, N, 9), 5), pr.gumbel_noise((1, E, N, 9), 6)])).to(DEV)
+    lg, vals, boot = f32(L, E, N, 9), f32(L + 1, E, N), f32(L, E, N)
     crit.value(vec.obs, out=vals[0])
-    traj = vec.rollout_policy(acts, K, noise=noise, trajectory=True, logits=lg, values=vals, boot=boot)
-    adv, ret = gae(traj["reward"], vals[:K], boot, traj["done"], 0.99, 0.95)
+    traj = vec.rollout_policy(acts, L, noise=noise, trajectory=True, logits=lg, values=vals, boot=boot)
+    t = ppo.transitions(traj, acts, lg, vals, boot)
+    adv, ret = gae(t["reward"], t["values"], t["boot"], t["done"], 0.99, 0.95)
     torch.cuda.synchronize()
-    return dict(obs=traj["obs"].clone(), done=traj["done"].clone(), acts=acts, logits=lg, vals=vals, boot=boot,
-                adv=adv, ret=ret)
+    return dict(obs=t["obs"].clone(), done=traj["done"][:K].clone(), acts=acts[:K + 1], logits=t["logits"], vals=vals[:K + 1],
+                boot=boot[:K], adv=adv, ret=ret)
 
 
 def ppo_loss(lg, old_logits, actions, adv, ret, v, clip=0.2):

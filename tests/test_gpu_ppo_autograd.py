@@ -45,22 +45,25 @@ def collect(H, nh, E=4, N=8, K=3, seed=37, sigma=0.3):
     pol, crit = seeded(MlpPolicy, od, H, nh, 1, sigma), seeded(MlpCritic, od, H, nh, 2)
     vec.set_policy(pol)
     vec.set_critic(crit)
+    L = K + 1  # a launch of K + 1 steps has K aligned decisions (ppo.transitions): the row counts stay K E N
     f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=DEV)
-    acts = torch.empty((K + 1, E, N, 3), dtype=torch.uint8, device=DEV)
+    acts = torch.empty((L + 1, E, N, 3), dtype=torch.uint8, device=DEV)
     pol.act(vec.obs, out=acts[0])
-    noise = torch.from_numpy(pr.gumbel_noise((K, E, N, 9), 5)).to(DEV)
-    lg, vals, boot = f32(K, E, N, 9), f32(K + 1, E, N), f32(K, E, N)
+    noise = torch.from_numpy(np.concatenate([pr.gumbel_noise((K, E, N, 9), 5), pr.gumbel_noise((1, E, N, 9), 6)])).to(DEV)
+    lg, vals, boot = f32(L, E, N, 9), f32(L + 1, E, N), f32(L, E, N)
     crit.value(vec.obs, out=vals[0])
-    traj = vec.rollout_policy(acts, K, noise=noise, trajectory=True, logits=lg, values=vals, boot=boot)
-    adv, ret = gae(traj["reward"], vals[:K], boot, traj["done"], 0.99, 0.95)
+    traj = vec.rollout_policy(acts, L, noise=noise, trajectory=True, logits=lg, values=vals, boot=boot)
+    t = ppo.transitions(traj, acts, lg, vals, boot)
+    adv, ret = gae(t["reward"], t["values"], t["boot"], t["done"], 0.99, 0.95)
     torch.cuda.synchronize()
+    lg = t["logits"]
     gen = torch.Generator(device=DEV)
     gen.manual_seed(3)
     old_logits = lg + 0.4 * torch.randn(lg.shape, device=DEV, generator=gen)  # the ratio leaves 1, some rows clip
-    actions = acts[1:].contiguous()
+    actions = t["actions"]
     pol.params.requires_grad_(True)
     crit.params.requires_grad_(True)
-    return dict(pol=pol, crit=crit, od=od, obs=traj["obs"].clone(), actions=actions, logits=lg, vals=vals, adv=adv,
+    return dict(pol=pol, crit=crit, od=od, obs=t["obs"].clone(), actions=actions, logits=lg, vals=t["values"], adv=adv,
                 ret=ret, old_logits=old_logits, old_logp=ppo.log_prob(old_logits, actions), rows=K * E * N)
 
 

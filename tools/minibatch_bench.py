@@ -80,6 +80,7 @@ def main():
     old_logits, vals, boot = f32(K, E, N, 9), f32(K + 1, E, N), f32(K, E, N)
     crit.value(vec.obs, out=vals[0])
     traj = vec.rollout_policy(acts, K, noise=noise, trajectory=True, logits=old_logits, values=vals, boot=boot)
+    # timing only: these rows are not aligned transitions (a learner takes them from gym_macm.ppo.transitions)
     adv, ret = gae(traj["reward"], vals[:K], boot, traj["done"], 0.99, 0.95)
     obs, actions, old_values = traj["obs"], acts[1:], vals[:K]
     old_logp = ppo.log_prob(old_logits, actions)
