@@ -361,3 +361,13 @@ int mlp_check(const std::string& noun, const M* m) {
   if (reinterpret_cast<uintptr_t>(m->params) & 15) return fail(MACM_E_INVALID, noun + ": params must be 16-byte aligned");
   return MACM_OK;
 }
+
+// A macm_sample_config as the kernels can take it, over `rows` rows: the flat row is a 32-bit counter word
+inline int sample_check(const macm_sample_config* cfg, int64_t rows) {
+  if (!cfg) return fail(MACM_E_INVALID, "sampling: cfg is NULL");
+  for (int i = 0; i < 4; ++i)
+    if (cfg->reserved[i] != 0) return fail(MACM_E_INVALID, "sampling: reserved must be 0");
+  if (rows < 0) return fail(MACM_E_INVALID, "sampling: rows must be >= 0");
+  if (rows > (int64_t)1 << 32) return fail(MACM_E_INVALID, "sampling: rows must be <= 2^32 (the row is a 32-bit counter word)");
+  return MACM_OK;
+}

@@ -24,6 +24,9 @@ struct macm_world {
   // macm_world_set_policy: the caller's params buffer, kept until replaced or cleared (params NULL: none)
   macm_policy_mlp policy{0, 0, 0, 0, nullptr};
   macm_value_mlp critic{0, 0, 0, 0, nullptr};  // macm_world_set_critic: likewise
+  // macm_world_set_sampling: the policy rollouts draw their own noise; sample.decision is the next launch's first
+  bool sampling = false;
+  SampleArgs sample{0, 0};
   uint32_t* hstat = nullptr;  // host-mapped status word (B.host_status is its device alias)
   unsigned long long* bad = nullptr;  // validate_actions: first failing row (device scratch)
   // workgroup-path rollouts: env slices on streams of their own (created on first use)
@@ -616,9 +619,11 @@ static int rollout_wg_slices(macm_world* w, int S, const unsigned char* actions,
 // macm_world_rollout_policy / _traj: the closed loop of bots = true with the registered policy as the
 // actor (pol: its params and this call's noise and logits; NULL: the scripted bot);
 // macm_world_rollout_policy_value / _traj: that with the registered critic beside the actor (crit: its
-// params and this call's values and boot; NULL: none)
+// params and this call's values and boot; NULL: none); smp: the policy draws its noise itself, the
+// decision after step k at smp->decision + k (a world with sampling on; NULL: pol->noise)
 static int world_rollout(macm_world* w, const void* actions, int n_steps, const macm_outputs* out, void* stream,
-                         bool bots, bool traj, const PolicyArgs* pol = nullptr, const ValueArgs* crit = nullptr) {
+                         bool bots, bool traj, const PolicyArgs* pol = nullptr, const ValueArgs* crit = nullptr,
+                         const SampleArgs* smp = nullptr) {
   if (n_steps < 0) return fail(MACM_E_INVALID, "n_steps must be >= 0");
   if (n_steps == 0) return MACM_OK;  // nothing is read, so actions may be NULL (an empty tensor)
   if (!w || !actions || !out || !out->reward) return fail(MACM_E_INVALID, "world/actions/out/reward is NULL");
@@ -647,6 +652,7 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
     x.debug = w->roll_reload;
     x.policy = pol;
     x.critic = crit;
+    x.sample = smp;
     if (w->autoreset)  // the kernels with the in-launch reset
       HIP_TRY(launch_rollout_ar_w64(w->P, w->B, w->cur, io, sh, x, ResetLaunch(w->mt, world_pose_draw(w), w->fin), s));
     else
@@ -694,8 +700,12 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
       PolicyArgs M = *pol;
       if (M.noise) M.noise += (size_t)k * rows * kPolicyLogits;
       if (M.logits && traj) M.logits += (size_t)k * rows * kPolicyLogits;
-      HIP_TRY(launch_policy_flock(M, ok.obs, w->cfg.obs_f64 != 0, obs_dim(w->cfg), rows,
-                                  const_cast<unsigned char*>(act_k) + (traj ? rows * 3 : 0), s));
+      unsigned char* const next = const_cast<unsigned char*>(act_k) + (traj ? rows * 3 : 0);
+      if (smp)  // the same draws as the wave path's launch
+        HIP_TRY(launch_policy_flock_sampled(M, SampleArgs{smp->seed, smp->decision + (unsigned long long)k}, ok.obs,
+                                            w->cfg.obs_f64 != 0, obs_dim(w->cfg), rows, next, s));
+      else
+        HIP_TRY(launch_policy_flock(M, ok.obs, w->cfg.obs_f64 != 0, obs_dim(w->cfg), rows, next, s));
     }
   }
   return MACM_OK;
@@ -741,14 +751,44 @@ int macm_world_set_policy(macm_world* w, const macm_policy_mlp* p) {
                        w ? &w->policy : nullptr);
 }
 
+// macm_world_set_sampling / _get_sampling: the draw as a property of the world (cfg NULL: off)
+int macm_world_set_sampling(macm_world* w, const macm_sample_config* cfg) {
+  if (!w) return fail(MACM_E_INVALID, "world is NULL");
+  if (!cfg) {
+    w->sampling = false;
+    w->sample = SampleArgs{0, 0};
+    return MACM_OK;
+  }
+  if (const int rc = sample_check(cfg, (int64_t)w->P.n_envs * w->P.n_agents)) return rc;
+  if (w->cfg.action_mode != MACM_ACTION_DISCRETE)
+    return fail(MACM_E_UNSUPPORTED, "sampling: the MLP policy acts in discrete mode (MultiDiscrete([3, 3, 3]))");
+  w->sampling = true;
+  w->sample = SampleArgs{cfg->seed, cfg->decision};
+  return MACM_OK;
+}
+
+int macm_world_get_sampling(macm_world* w, macm_sample_config* cfg_out) {
+  if (!w || !cfg_out) return fail(MACM_E_INVALID, "world/cfg_out is NULL");
+  *cfg_out = macm_sample_config{w->sample.seed, w->sample.decision, {0, 0, 0, 0}};
+  return w->sampling ? 1 : 0;
+}
+
+static const char* const kNoiseAndSampling =
+    "noise is given while sampling is on (macm_world_set_sampling): the launch draws its own; nothing was launched";
+// the draw of a policy rollout of w (NULL: sampling is off)
+static const SampleArgs* world_sample(const macm_world* w) { return w->sampling ? &w->sample : nullptr; }
+
 static int world_rollout_policy(macm_world* w, uint8_t* actions, int n_steps, const float* noise, float* logits,
                                 const macm_outputs* out, void* stream, bool traj) {
   if (n_steps < 0) return fail(MACM_E_INVALID, "n_steps must be >= 0");
   if (n_steps == 0) return MACM_OK;
   if (!w) return fail(MACM_E_INVALID, "world is NULL");
   if (!w->policy.params) return fail(MACM_E_INVALID, "no policy is registered (macm_world_set_policy)");
+  if (w->sampling && noise) return fail(MACM_E_INVALID, kNoiseAndSampling);
   const PolicyArgs M{w->policy.params, noise, logits, w->policy.hidden, w->policy.n_hidden};
-  return world_rollout(w, actions, n_steps, out, stream, true, traj, &M);
+  const int rc = world_rollout(w, actions, n_steps, out, stream, true, traj, &M, nullptr, world_sample(w));
+  if (rc == MACM_OK && w->sampling) w->sample.decision += (unsigned long long)n_steps;
+  return rc;
 }
 
 int macm_world_rollout_policy(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise, float* logits,
@@ -775,9 +815,12 @@ static int world_rollout_policy_value(macm_world* w, uint8_t* actions, int n_ste
     return fail(MACM_E_INVALID, "values and boot are both NULL (macm_world_rollout_policy serves that case)");
   if (!w->policy.params) return fail(MACM_E_INVALID, "no policy is registered (macm_world_set_policy)");
   if (!w->critic.params) return fail(MACM_E_INVALID, "no critic is registered (macm_world_set_critic)");
+  if (w->sampling && noise) return fail(MACM_E_INVALID, kNoiseAndSampling);
   const PolicyArgs M{w->policy.params, noise, logits, w->policy.hidden, w->policy.n_hidden};
   const ValueArgs V{w->critic.params, values, boot, w->critic.hidden, w->critic.n_hidden};
-  return world_rollout(w, actions, n_steps, out, stream, true, traj, &M, &V);
+  const int rc = world_rollout(w, actions, n_steps, out, stream, true, traj, &M, &V, world_sample(w));
+  if (rc == MACM_OK && w->sampling) w->sample.decision += (unsigned long long)n_steps;
+  return rc;
 }
 
 int macm_world_rollout_policy_value(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise, float* logits,

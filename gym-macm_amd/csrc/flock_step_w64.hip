@@ -2781,12 +2781,21 @@ struct ObsPol {};
 // their argument grows by the critic's fields after the policy's.
 template <typename OT>
 struct ObsPolV {};
+// ... and of a world with sampling on (macm_world_set_sampling): ObsPolS / ObsPolVS, the ObsPol / ObsPolV
+// kernels with the draw of policy_sample.hpp where the noise is read; their argument grows by the seed
+// and the launch's first decision index after the fields before. New tags, so that the kernels above
+// keep their names and their code.
+template <typename OT>
+struct ObsPolS {};
+template <typename OT>
+struct ObsPolVS {};
 template <typename OTA>
 struct ObsTag {
   using type = OTA;
   static constexpr bool ev = false;
   static constexpr bool pol = false;
   static constexpr bool val = false;
+  static constexpr bool smp = false;
 };
 template <typename OT>
 struct ObsTag<ObsEv<OT>> {
@@ -2794,6 +2803,7 @@ struct ObsTag<ObsEv<OT>> {
   static constexpr bool ev = true;
   static constexpr bool pol = false;
   static constexpr bool val = false;
+  static constexpr bool smp = false;
 };
 template <typename OT>
 struct ObsTag<ObsPol<OT>> {
@@ -2801,6 +2811,7 @@ struct ObsTag<ObsPol<OT>> {
   static constexpr bool ev = false;
   static constexpr bool pol = true;
   static constexpr bool val = false;
+  static constexpr bool smp = false;
 };
 template <typename OT>
 struct ObsTag<ObsPolV<OT>> {
@@ -2808,6 +2819,15 @@ struct ObsTag<ObsPolV<OT>> {
   static constexpr bool ev = false;
   static constexpr bool pol = true;
   static constexpr bool val = true;
+  static constexpr bool smp = false;
+};
+template <typename OT>
+struct ObsTag<ObsPolS<OT>> : ObsTag<ObsPol<OT>> {
+  static constexpr bool smp = true;
+};
+template <typename OT>
+struct ObsTag<ObsPolVS<OT>> : ObsTag<ObsPolV<OT>> {
+  static constexpr bool smp = true;
 };
 template <typename OT>
 struct RolloutArgs<ObsEv<OT>> : RolloutArgs<OT> {
@@ -2823,6 +2843,14 @@ struct RolloutArgs<ObsPolV<OT>> : RolloutArgs<ObsPol<OT>> {
   // values [E, N], or [K + 1, E, N] with traj: step k writes row k + 1; boot [E, N], or [K, E, N] with traj
   ValueArgs val;
 };
+template <typename OT>
+struct RolloutArgs<ObsPolS<OT>> : RolloutArgs<ObsPol<OT>> {
+  SampleArgs smp;  // the decision after step k draws at smp.decision + k (pol.noise is not read)
+};
+template <typename OT>
+struct RolloutArgs<ObsPolVS<OT>> : RolloutArgs<ObsPolV<OT>> {
+  SampleArgs smp;
+};
 // One lane's critic stores of step k of a policy rollout: v is the bootstrap value of the step's output
 // row kr (with_boot) and the value of the obs row the next action is taken from
 __device__ __forceinline__ void value_store_row(const ValueArgs& V, float v, size_t row, size_t k, size_t kr, size_t EN,
@@ -2837,6 +2865,16 @@ __device__ __forceinline__ void policy_act_row(const PolicyArgs& M, int od, cons
                                                size_t k, size_t kr, size_t EN, uint8_t* __restrict__ pol_out) {
   policy_mlp_row<OT>(M, od, obs + row * od, M.noise ? M.noise + (k * EN + row) * kPolicyLogits : nullptr,
                      pol_out + row * 3, M.logits ? M.logits + (kr * EN + row) * kPolicyLogits : nullptr);
+}
+// ... of a sampled rollout: the row draws at decision S.decision + k. The row is the env's, not the
+// wave's: rollout_sched reorders the waves.
+template <typename OT>
+__device__ __forceinline__ void policy_sample_row(const PolicyArgs& M, const SampleArgs& S, int od,
+                                                  const OT* __restrict__ obs, size_t row, size_t k, size_t kr, size_t EN,
+                                                  uint8_t* __restrict__ pol_out) {
+  policy_mlp_row<OT, true>(M, od, obs + row * od, nullptr, pol_out + row * 3,
+                           M.logits ? M.logits + (kr * EN + row) * kPolicyLogits : nullptr,
+                           SampleDraw{S.seed, S.decision + k, (uint32_t)row});
 }
 // Carried Flock rollouts (CARRY) only: this bit of RolloutArgs::cur is MACM_DEBUG_ROLLOUT_RELOAD, every
 // step loads its state and waits for the stores of the step before, as a rollout without the carry.
@@ -2898,7 +2936,7 @@ struct TypeTag {
 };
 
 // The variant of a rollout kernel a launch takes, for env_rollout_w64 and env_rollout_ar_w64 alike:
-// go(TypeTag<OTA>, carry, fill) with OTA = OT or its ObsEv / ObsPol / ObsPolV tag, carry = CARRY as a
+// go(TypeTag<OTA>, carry, fill) with OTA = OT or its ObsEv / ObsPol / ObsPolV / ObsPolS / ObsPolVS tag, carry = CARRY as a
 // bool_constant and fill(R) setting the fields the tagged argument adds. Flock: the carried step where
 // the actions are given (closed = false), else the policy with or without the critic, else the bot;
 // TDM: the kernel that records the events where hit_out is set. `cur` takes the debug bits.
@@ -2911,10 +2949,21 @@ static void roll_variant(int& cur, bool closed, const FlockRollExtras& x, int32_
       if (x.debug & 1) cur |= kRollReloadBit;
       return go(TypeTag<OT>{}, std::true_type{}, none);
     }
+    if (x.policy && x.critic && x.sample)
+      return go(TypeTag<ObsPolVS<OT>>{}, std::false_type{}, [&](auto& R) {
+        R.pol = *x.policy;
+        R.val = *x.critic;
+        R.smp = *x.sample;
+      });
     if (x.policy && x.critic)
       return go(TypeTag<ObsPolV<OT>>{}, std::false_type{}, [&](auto& R) {
         R.pol = *x.policy;
         R.val = *x.critic;
+      });
+    if (x.policy && x.sample)
+      return go(TypeTag<ObsPolS<OT>>{}, std::false_type{}, [&](auto& R) {
+        R.pol = *x.policy;
+        R.smp = *x.sample;
       });
     if (x.policy) return go(TypeTag<ObsPol<OT>>{}, std::false_type{}, [&](auto& R) { R.pol = *x.policy; });
   } else if (hit_out) {
@@ -2970,6 +3019,7 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
   constexpr bool EV = ObsTag<OTA>::ev;
   constexpr bool POL = ObsTag<OTA>::pol;
   constexpr bool VAL = ObsTag<OTA>::val;
+  constexpr bool SMP = ObsTag<OTA>::smp;
   static_assert(!EV || MODE == kTdm, "combat events are TDM's");
   static_assert(!POL || (MODE == kFlock && !CARRY), "the MLP policy acts in Flock's closed loop");
   const int nsteps = A0.nsteps;
@@ -3060,7 +3110,9 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
           if constexpr (VAL)  // no reset here: the step's obs row is the row the next action is taken from
             value_store_row(A.val, value_mlp_row<OT>(A.val, (int)od, obs + row * od), row, (size_t)k, kr, EN, A.traj != 0,
                             true);
-          if constexpr (POL)
+          if constexpr (SMP)
+            policy_sample_row<OT>(A.pol, A.smp, (int)od, obs, row, (size_t)k, kr, EN, pol_out);
+          else if constexpr (POL)
             policy_act_row<OT>(A.pol, (int)od, obs, row, (size_t)k, kr, EN, pol_out);
           else if constexpr (MODE == kTdm)
             bot_combat_row(obs + row * (N - 1) * 4, TB.mask_out + row * (N - 1), N, pol_out + row * 4);

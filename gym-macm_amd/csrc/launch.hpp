@@ -56,12 +56,13 @@ struct ResetLaunch {
 };
 
 // A Flock rollout's extras: debug bit 0 MACM_DEBUG_ROLLOUT_RELOAD (load and fence every step), bit 1
-// MACM_DEBUG_NEAR_PLAIN; the closed loop's MLP policy where the bot is (NULL: the bot) and the critic
-// beside it (NULL: none)
+// MACM_DEBUG_NEAR_PLAIN; the closed loop's MLP policy where the bot is (NULL: the bot), the critic
+// beside it (NULL: none) and the policy's own draw (worlds with sampling on; NULL: it reads policy->noise)
 struct FlockRollExtras {
   int debug = 0;
   const PolicyArgs* policy = nullptr;
   const ValueArgs* critic = nullptr;
+  const SampleArgs* sample = nullptr;
 };
 
 // launch_final_copy's sources: the step's output rows ([E, ...]) and their sizes per env

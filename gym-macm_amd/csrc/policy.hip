@@ -1,8 +1,9 @@
 // policy.hip — a learned MLP policy over observation rows (macm_policy_flock): the decision of
 // policy_mlp.hpp for every row, one lane per row, as bots.hip is for the scripted bot. The first
 // actions of a closed loop come from here (on the initial obs), and the per-step loop of the
-// workgroup path calls it after every step. Beside it the critic over rows (macm_value_flock) and the
-// advantages of a trajectory (macm_gae).
+// workgroup path calls it after every step. Beside it the same decision with the Gumbel draw inside
+// (macm_policy_flock_sampled) and the noise of that draw as a tensor (macm_policy_noise), both on
+// policy_sample.hpp; the critic over rows (macm_value_flock) and the advantages of a trajectory (macm_gae).
 #include "policy_mlp.hpp"
 
 namespace macm {
@@ -25,6 +26,63 @@ hipError_t launch_policy_flock(const PolicyArgs& M, const void* obs, bool obs_f6
     hipLaunchKernelGGL(policy_flock_kernel<double>, grid, dim3(B), 0, s, M, (const double*)obs, od, rows, act);
   else
     hipLaunchKernelGGL(policy_flock_kernel<float>, grid, dim3(B), 0, s, M, (const float*)obs, od, rows, act);
+  return hipGetLastError();
+}
+
+// policy_flock_kernel with the draw inside (macm_policy_flock_sampled): row i draws at decision S.decision
+template <typename OT>
+__global__ __launch_bounds__(256) void policy_flock_sampled_kernel(PolicyArgs M, SampleArgs S, const OT* __restrict__ obs,
+                                                                   int od, long long rows, uint8_t* __restrict__ act) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows) return;
+  policy_mlp_row<OT, true>(M, od, obs + i * od, nullptr, act + i * 3, M.logits ? M.logits + i * kPolicyLogits : nullptr,
+                           SampleDraw{S.seed, S.decision, (uint32_t)i});
+}
+
+hipError_t launch_policy_flock_sampled(const PolicyArgs& M, const SampleArgs& S, const void* obs, bool obs_f64, int od,
+                                       long long rows, uint8_t* act, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  const int B = 256;
+  const dim3 grid((unsigned)((rows + B - 1) / B));
+  if (obs_f64)
+    hipLaunchKernelGGL(policy_flock_sampled_kernel<double>, grid, dim3(B), 0, s, M, S, (const double*)obs, od, rows, act);
+  else
+    hipLaunchKernelGGL(policy_flock_sampled_kernel<float>, grid, dim3(B), 0, s, M, S, (const float*)obs, od, rows, act);
+  return hipGetLastError();
+}
+
+// The noise itself (macm_policy_noise): thread = row, blockIdx.y strides over the decisions; the words
+// as the generator gave them beside it, for the tests
+constexpr int kNoiseMaxGridY = 65535;
+__global__ __launch_bounds__(256) void policy_noise_kernel(SampleArgs S, long long n_dec, long long rows,
+                                                           float* __restrict__ noise, uint32_t* __restrict__ words) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows) return;
+  for (long long j = blockIdx.y; j < n_dec; j += gridDim.y) {
+    const SampleDraw sd{S.seed, S.decision + (unsigned long long)j, (uint32_t)i};
+    const size_t at = (size_t)j * (size_t)rows + (size_t)i;
+#pragma unroll
+    for (int h = 0; h < 3; ++h) {
+      float g[3];
+      gumbel_row(sd, h, g);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) noise[at * kPolicyLogits + 3 * h + c] = g[c];
+      if (words) {
+        uint32_t w[4];
+        sample_words(sd, h, w);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) words[(at * 3 + h) * 4 + q] = w[q];
+      }
+    }
+  }
+}
+
+hipError_t launch_policy_noise(const SampleArgs& S, long long n_dec, long long rows, float* noise, uint32_t* words,
+                               hipStream_t s) {
+  if (n_dec <= 0 || rows <= 0) return hipSuccess;
+  const int B = 256;
+  const dim3 grid((unsigned)((rows + B - 1) / B), (unsigned)(n_dec < kNoiseMaxGridY ? n_dec : kNoiseMaxGridY));
+  hipLaunchKernelGGL(policy_noise_kernel, grid, dim3(B), 0, s, S, n_dec, rows, noise, words);
   return hipGetLastError();
 }
 

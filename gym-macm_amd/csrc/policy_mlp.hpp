@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "policy_sample.hpp"
+
 namespace macm {
 
 constexpr int kPolicyLogits = 9;  // MultiDiscrete([3, 3, 3]): head h at logits[3h + c]
@@ -49,10 +51,13 @@ __device__ __forceinline__ void policy_layer(policy_cptr W, policy_cptr b, const
   }
 }
 
-template <typename OT, int OD, int H>
+// SMP (the sampled form, policy_sample.hpp): the noise is the draw sd's, not read; it is produced head
+// by head after the logits are stored, when the MLP's activations are dead, and consumed at once by
+// the running argmax
+template <typename OT, int OD, int H, bool SMP = false>
 __device__ __forceinline__ void policy_mlp_row_t(policy_cptr p, int n_hidden, const OT* __restrict__ o,
                                                  const float* __restrict__ noise, uint8_t* __restrict__ act,
-                                                 float* __restrict__ logits) {
+                                                 float* __restrict__ logits, const SampleDraw& sd = SampleDraw{}) {
   float x[OD];
 #pragma unroll
   for (int q = 0; q < OD; ++q) x[q] = (float)o[q];
@@ -72,12 +77,20 @@ __device__ __forceinline__ void policy_mlp_row_t(policy_cptr p, int n_hidden, co
 #pragma unroll
     for (int j = 0; j < kPolicyLogits; ++j) logits[j] = y[j];
   }
-  if (noise) {
+  if constexpr (!SMP) {
+    if (noise) {
 #pragma unroll
-    for (int j = 0; j < kPolicyLogits; ++j) y[j] = y[j] + noise[j];
+      for (int j = 0; j < kPolicyLogits; ++j) y[j] = y[j] + noise[j];
+    }
   }
 #pragma unroll
   for (int hd = 0; hd < 3; ++hd) {
+    if constexpr (SMP) {
+      float g[3];
+      gumbel_row(sd, hd, g);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) y[3 * hd + c] = y[3 * hd + c] + g[c];
+    }
     int best = 0;
     float bz = -__builtin_inff();
 #pragma unroll
@@ -93,21 +106,22 @@ __device__ __forceinline__ void policy_mlp_row_t(policy_cptr p, int n_hidden, co
 
 // o: the agent's obs row (od = 4 polar / 6 cartesian) as stored; noise / logits: its 9 floats or NULL;
 // act: its 3 action bytes. M.params, M.hidden and M.n_hidden must be wave-uniform.
-template <typename OT>
+// SMP: the row draws its noise itself (sd; `noise` is not read)
+template <typename OT, bool SMP = false>
 __device__ __forceinline__ void policy_mlp_row(const PolicyArgs& M, int od, const OT* __restrict__ o,
                                                const float* __restrict__ noise, uint8_t* __restrict__ act,
-                                               float* __restrict__ logits) {
+                                               float* __restrict__ logits, const SampleDraw& sd = SampleDraw{}) {
   const policy_cptr p = (policy_cptr)(unsigned long long)M.params;
   if (od == 6) {
     if (M.hidden == 32)
-      policy_mlp_row_t<OT, 6, 32>(p, M.n_hidden, o, noise, act, logits);
+      policy_mlp_row_t<OT, 6, 32, SMP>(p, M.n_hidden, o, noise, act, logits, sd);
     else
-      policy_mlp_row_t<OT, 6, 16>(p, M.n_hidden, o, noise, act, logits);
+      policy_mlp_row_t<OT, 6, 16, SMP>(p, M.n_hidden, o, noise, act, logits, sd);
   } else {
     if (M.hidden == 32)
-      policy_mlp_row_t<OT, 4, 32>(p, M.n_hidden, o, noise, act, logits);
+      policy_mlp_row_t<OT, 4, 32, SMP>(p, M.n_hidden, o, noise, act, logits, sd);
     else
-      policy_mlp_row_t<OT, 4, 16>(p, M.n_hidden, o, noise, act, logits);
+      policy_mlp_row_t<OT, 4, 16, SMP>(p, M.n_hidden, o, noise, act, logits, sd);
   }
 }
 
@@ -169,6 +183,13 @@ hipError_t launch_gae(const float* reward, const float* values, const float* boo
                       const GaeShape& g, float* adv, float* ret, hipStream_t s);
 hipError_t launch_policy_flock(const PolicyArgs& M, const void* obs, bool obs_f64, int od, long long rows,
                                uint8_t* act, hipStream_t s);
+// launch_policy_flock with the draw inside: row r at decision S.decision (M.noise is not read)
+hipError_t launch_policy_flock_sampled(const PolicyArgs& M, const SampleArgs& S, const void* obs, bool obs_f64, int od,
+                                       long long rows, uint8_t* act, hipStream_t s);
+// the noise decisions S.decision .. + n_dec - 1 draw for rows r < rows: noise [n_dec, rows, 9], and the raw
+// words [n_dec, rows, 3, 4] (or NULL)
+hipError_t launch_policy_noise(const SampleArgs& S, long long n_dec, long long rows, float* noise, uint32_t* words,
+                               hipStream_t s);
 
 // host side, policy_grad.hip: dL/dparams of either net (n_out = 9: the policy, 1: the critic) from dout
 // [rows, n_out] (macm_policy_grad / macm_value_grad). One wave writes one partial [n_params] into the

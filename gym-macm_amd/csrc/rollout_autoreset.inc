@@ -207,6 +207,16 @@ struct RolloutArArgs<ObsPolV<OT>> : RolloutArArgs<ObsPol<OT>> {
   ValueArgs val;  // values [E, N] or [K + 1, E, N], boot [E, N] or [K, E, N] with A.traj
 };
 
+// a world with sampling on (ObsPolS / ObsPolVS): the draw's two words follow
+template <typename OT>
+struct RolloutArArgs<ObsPolS<OT>> : RolloutArArgs<ObsPol<OT>> {
+  SampleArgs smp;  // the decision after step k draws at smp.decision + k (pol.noise is not read)
+};
+template <typename OT>
+struct RolloutArArgs<ObsPolVS<OT>> : RolloutArArgs<ObsPolV<OT>> {
+  SampleArgs smp;
+};
+
 // env_rollout_w64 with the in-launch reset; no tail or split observation (their pose snapshots know
 // nothing of a mid-launch respawn: TDM observes inside the step).
 // OTA: OT or ObsEv<OT>, as env_rollout_w64. The step writes the events, the in-launch reset none: it
@@ -217,6 +227,7 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
   constexpr bool EV = ObsTag<OTA>::ev;
   constexpr bool POL = ObsTag<OTA>::pol;
   constexpr bool VAL = ObsTag<OTA>::val;
+  constexpr bool SMP = ObsTag<OTA>::smp;
   static_assert(!EV || MODE == kTdm, "combat events are TDM's");
   static_assert(!POL || (MODE == kFlock && !CARRY), "the MLP policy acts in Flock's closed loop");
   const int nsteps = R0.A.nsteps;
@@ -329,7 +340,9 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
         uint8_t* const pol_out = A.traj ? pol_in + EN * abytes : pol_in;
         if (lane < N) {
           const size_t row = (size_t)env * N + lane;
-          if constexpr (POL)
+          if constexpr (SMP)  // a reset env: the same decision index as the noise row k it would have read
+            policy_sample_row<OT>(R.pol, R.smp, (int)od, obs, row, (size_t)k, kr, EN, pol_out);
+          else if constexpr (POL)
             policy_act_row<OT>(R.pol, (int)od, obs, row, (size_t)k, kr, EN, pol_out);
           else if constexpr (MODE == kTdm)
             bot_combat_row(obs + row * (N - 1) * 4, TB.mask_out + row * (N - 1), N, pol_out + row * 4);

@@ -96,6 +96,12 @@ class MacmValueMlp(Structure):
                 ("params", c_void_p)]
 
 
+class MacmSampleConfig(Structure):
+    """macm_sample_config: the key of the in-launch Gumbel draw and the index of the first decision;
+    reserved is 0."""
+    _fields_ = [("seed", c_uint64), ("decision", c_uint64), ("reserved", c_int32 * 4)]
+
+
 class MacmPpoConfig(Structure):
     """macm_ppo_config: the clip range, the coefficients of the value loss and of the entropy bonus, and the
     value clip range (read only where old values are given); reserved is 0."""
@@ -285,6 +291,11 @@ SIGNATURES = {
                                           c_void_p]),
     "macm_world_rollout_policy_traj": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, POINTER(MacmOutputs),
                                                c_void_p]),
+    "macm_policy_noise": (c_int, [POINTER(MacmSampleConfig), c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "macm_policy_flock_sampled": (c_int, [POINTER(MacmPolicyMlp), c_void_p, c_int32, c_int64, POINTER(MacmSampleConfig),
+                                          c_void_p, c_void_p, c_void_p]),
+    "macm_world_set_sampling": (c_int, [c_void_p, POINTER(MacmSampleConfig)]),
+    "macm_world_get_sampling": (c_int, [c_void_p, POINTER(MacmSampleConfig)]),
     "macm_value_flock": (c_int, [POINTER(MacmValueMlp), c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
     "macm_world_set_critic": (c_int, [c_void_p, POINTER(MacmValueMlp)]),
     "macm_world_rollout_policy_value": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1,15 +1,19 @@
 """A learned policy as the actor of Flock's closed loop: a float32 MLP over every agent's obs row.
 
     pol = MlpPolicy.from_linear_layers([net.l1, net.l2, net.head], device="cuda:0")
-    act = pol.act(vec.obs)                          # the first actions, uint8 [E, N, 3]
-    vec.set_policy(pol)
-    out = vec.rollout_policy(act, 128, noise=gumbel, trajectory=True)   # one launch on the wave path
+    acts[0] = pol.act(vec.obs, seed=seed, decision=0)   # the first actions, uint8 [E, N, 3], sampled
+    vec.set_policy(pol); vec.set_sampling(seed, decision=1)
+    out = vec.rollout_policy(acts, 128, trajectory=True)   # one launch on the wave path; it draws its own noise
 
 The definition is include/macm.h's (macm_policy_mlp): ``y[j] = b[j] + sum_k W[k][j] x[k]`` as the
 k-ordered float32 fmaf chain, relu on the hidden layers, 9 logits (head h of MultiDiscrete([3, 3, 3])
 at ``logits[3h + c]``), ``action[h] = argmax_c(logits[3h + c] + noise[3h + c])``, the lowest index on
-ties. The caller supplies the noise (Gumbel noise samples from the softmax; None is the argmax) and
-recomputes log-probabilities from the stored logits; the device draws nothing.
+ties. Gumbel noise samples from the softmax; None is the argmax. A world with sampling on
+(``set_sampling``) and ``act(seed=, decision=)`` draw it inside the launch from a counter-based generator
+(macm_sample_config: Philox4x32-10 over (seed, decision index, row, head), g = -log(-log(u)) in float64),
+reproducible however the steps are cut into launches; ``gumbel_noise`` gives the same numbers as a tensor
+for a caller who wants to pass ``noise`` explicitly. The learner recomputes log-probabilities from the
+stored logits.
 
 ``params`` is one flat device tensor, W[in][out] row-major then the bias, layer after layer. The
 library reads it at every launch, so a learner that writes new values into it in place
@@ -21,7 +25,7 @@ and ``gae`` turns a trajectory into advantages and returns in one launch:
     crit = MlpCritic.from_linear_layers([v.fc1, v.fc2, v.head], device="cuda:0"); vec.set_critic(crit)
     vals = torch.empty((K + 1, E, N), device=dev); vals[0] = crit.value(vec.obs)
     boot = torch.empty((K, E, N), device=dev)
-    traj = vec.rollout_policy(acts, K, noise=g, trajectory=True, logits=lg, values=vals, boot=boot)
+    traj = vec.rollout_policy(acts, K, trajectory=True, logits=lg, values=vals, boot=boot)
     t = ppo.transitions(traj, acts, lg, vals, boot)   # gym_macm.ppo: each decision beside its own step, as views
     adv, ret = gae(t["reward"], t["values"], t["boot"], t["done"], 0.99, 0.95)
 
@@ -214,9 +218,11 @@ class MlpPolicy(_Mlp):
         return logits
 
     def act(self, obs: torch.Tensor, noise: torch.Tensor = None, logits: torch.Tensor = None,
-            out: torch.Tensor = None) -> torch.Tensor:
+            out: torch.Tensor = None, seed: int = None, decision: int = 0) -> torch.Tensor:
         """The policy's actions (uint8 [..., 3]) for obs [..., in_dim] (macm_policy_flock); noise and
-        logits: float32 [..., 9] or None (logits is written)."""
+        logits: float32 [..., 9] or None (logits is written). With ``seed`` the launch draws the noise itself
+        (macm_policy_flock_sampled): flat row r of obs at decision index ``decision``, the numbers of
+        ``gumbel_noise(seed, decision, 1, obs.shape[:-1])``; ``noise`` must then be None."""
         if obs.device != self.device or not obs.is_contiguous() or obs.dtype not in (torch.float32, torch.float64):
             raise ValueError("obs must be a contiguous float32/float64 tensor on the policy's device")
         if obs.shape[-1] != self.in_dim:
@@ -233,6 +239,16 @@ class MlpPolicy(_Mlp):
             raise ValueError(f"out must be a contiguous uint8 {lead + (3,)} tensor on the policy's device")
         p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         L = _abi.lib()
+        if seed is not None:
+            if noise is not None:
+                raise ValueError("noise and seed exclude each other: with seed the launch draws its own noise")
+            cfg = sample_config(seed, decision)
+            with torch.cuda.device(self.device):
+                _abi.check(L.macm_policy_flock_sampled(ctypes.byref(self._struct), p(obs),
+                                                       1 if obs.dtype == torch.float64 else 0, obs.numel() // self.in_dim,
+                                                       ctypes.byref(cfg), p(out), p(logits), _stream(obs)),
+                           "macm_policy_flock_sampled")
+            return out
         with torch.cuda.device(self.device):
             _abi.check(L.macm_policy_flock(ctypes.byref(self._struct), p(obs), 1 if obs.dtype == torch.float64 else 0,
                                            obs.numel() // self.in_dim, p(noise), p(out), p(logits), _stream(obs)),
@@ -301,6 +317,41 @@ def gae(reward: torch.Tensor, values: torch.Tensor, boot: torch.Tensor, done: to
         _abi.check(_abi.lib().macm_gae(p(reward), p(values), p(boot), p(done), K, E, N, float(gamma), float(lam),
                                        p(adv), p(ret), _stream(reward)), "macm_gae")
     return adv, ret
+
+
+def sample_config(seed: int, decision: int = 0) -> "_abi.MacmSampleConfig":
+    """macm_sample_config from Python ints; ValueError outside [0, 2**64)."""
+    seed, decision = int(seed), int(decision)
+    if not (0 <= seed < 1 << 64) or not (0 <= decision < 1 << 64):
+        raise ValueError("seed and decision must be in [0, 2**64)")
+    return _abi.MacmSampleConfig(seed, decision, (ctypes.c_int32 * 4)(0, 0, 0, 0))
+
+
+def gumbel_noise(seed: int, decision: int, n_dec: int, rows_shape, device=None, words: bool = False):
+    """The Gumbel noise that decisions ``decision .. decision + n_dec - 1`` draw under ``seed`` for the rows of
+    ``rows_shape`` (e.g. (E, N); row r is the flat index), float32 [n_dec, *rows_shape, 9], in one launch
+    (macm_policy_noise): what a sampling world adds to its logits, bit for bit, so
+    ``rollout_policy(noise=gumbel_noise(seed, d, K, (E, N)))`` on a world without sampling is the twin of the
+    launch a world with ``set_sampling(seed, d)`` makes. With ``words`` also the generator's raw output:
+    (noise, words), words int32 [n_dec, *rows_shape, 3, 4] holding the uint32 bits (``.cpu().numpy().view(np.uint32)``)."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("gumbel_noise runs on a GPU device (no CPU fallback)")
+    shape = tuple(int(d) for d in (rows_shape if hasattr(rows_shape, "__iter__") else (rows_shape,)))
+    rows = 1
+    for d in shape:
+        rows *= d
+    n_dec = int(n_dec)
+    cfg = sample_config(seed, decision)
+    noise = torch.empty((n_dec,) + shape + (N_LOGITS,), dtype=torch.float32, device=device)
+    w = torch.empty((n_dec,) + shape + (3, 4), dtype=torch.int32, device=device) if words else None
+    with torch.cuda.device(device):
+        _abi.check(_abi.lib().macm_policy_noise(ctypes.byref(cfg), n_dec, rows, ctypes.c_void_p(noise.data_ptr()),
+                                                ctypes.c_void_p(w.data_ptr()) if words else None, _stream(noise)),
+                   "macm_policy_noise")
+    return (noise, w) if words else noise
 
 
 def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:

@@ -131,11 +131,22 @@ class FlockVec(object):
         (World.set_critic)."""
         self.world.set_critic(critic)
 
+    def set_sampling(self, seed, decision: int = 0) -> None:
+        """Sample the actions of rollout_policy inside the launch (World.set_sampling): no noise tensor,
+        reproducible from (seed, decision index) however the steps are cut into launches. ``seed=None``: off."""
+        self.world.set_sampling(seed, decision)
+
+    @property
+    def sampling(self):
+        """(seed, next decision index) with sampling on, else None (World.sampling)."""
+        return self.world.sampling
+
     def rollout_policy(self, actions, n_steps, noise=None, trajectory=False, traj=None, logits=None, values=None,
                        boot=None):
         """n_steps of the closed loop step -> policy -> step in one launch, beside rollout_bots: the
         registered MlpPolicy acts on the observation each step wrote (World.rollout_policy). ``noise``
-        [n_steps, E, N, 9] samples (None: argmax); ``logits`` keeps what the policy computed. With
+        [n_steps, E, N, 9] samples (None: argmax, or after ``set_sampling`` the launch's own draw);
+        ``logits`` keeps what the policy computed. With
         ``autoreset`` an env that ends restarts inside the launch and acts on its new initial obs.
         ``values`` / ``boot``: the registered critic's V of every row and the bootstrap value of every
         step, from the same launch."""

@@ -362,6 +362,30 @@ class World:
         _abi.check(self.L.macm_world_set_critic(self.h, ctypes.byref(critic.struct())), "macm_world_set_critic")
         self.critic = critic
 
+    def set_sampling(self, seed, decision: int = 0) -> None:
+        """In-launch action sampling (macm_world_set_sampling; off at creation): while it is on,
+        ``rollout_policy(noise=None)`` draws its own Gumbel noise, the decision after step k of a launch
+        at decision index ``decision + k``, and each launch advances the world's ``decision`` by its
+        n_steps: K = 7 then K = 13 samples exactly what K = 20 does. The numbers are
+        ``gym_macm.policy.gumbel_noise(seed, decision, K, (E, N))``. ``seed=None`` turns it off (None is
+        the argmax again). With sampling on, passing ``noise`` raises MacmError."""
+        if seed is None:
+            _abi.check(self.L.macm_world_set_sampling(self.h, None), "macm_world_set_sampling")
+            return
+        from .policy import sample_config
+        cfg = sample_config(seed, decision)
+        _abi.check(self.L.macm_world_set_sampling(self.h, ctypes.byref(cfg)), "macm_world_set_sampling")
+
+    @property
+    def sampling(self):
+        """(seed, decision) with sampling on, ``decision`` the index the next launch starts at; None with it off
+        (macm_world_get_sampling; host state, no synchronisation)."""
+        cfg = _abi.MacmSampleConfig()
+        rc = self.L.macm_world_get_sampling(self.h, ctypes.byref(cfg))
+        if rc < 0:
+            _abi.check(rc, "macm_world_get_sampling")
+        return (int(cfg.seed), int(cfg.decision)) if rc == 1 else None
+
     def rollout_policy(self, actions: torch.Tensor, n_steps: int, noise: torch.Tensor = None, trajectory: bool = False,
                        traj: dict = None, logits: torch.Tensor = None, values: torch.Tensor = None,
                        boot: torch.Tensor = None):
@@ -369,7 +393,8 @@ class World:
         one launch on the wave path (macm_world_rollout_policy / _traj), as rollout_bots is for the bot.
         actions: uint8 [E, N, 3], the first step's on entry (``policy.act(self.obs)``) and the next on
         return; with ``trajectory`` [n_steps + 1, E, N, 3], row 0 given and step k writing row k + 1.
-        noise: float32 [n_steps, E, N, 9] or None (argmax); row k decides after step k.
+        noise: float32 [n_steps, E, N, 9] or None (argmax; on a world with ``set_sampling`` on, None: the
+        launch draws its own, and advances ``sampling``'s decision by n_steps); row k decides after step k.
         logits: float32 [E, N, 9] (the last step's remain), with ``trajectory`` [n_steps, E, N, 9], or
         None; row k holds the logits computed from obs row k.
         values / boot: with either given, the registered critic runs beside the actor

@@ -481,7 +481,8 @@ int macm_world_rollout_bots_traj(macm_world* w, uint8_t* actions, int32_t n_step
  *           action[h] = the lowest c with the largest z: best = 0, top = -inf, then for c = 0, 1, 2
  *           `if (z[c] > top) best = c, top = z[c]`, so a NaN is never chosen over a number.
  * Denormals are kept; the sign and payload of a NaN logit are unspecified. The caller supplies the noise (Gumbel noise for sampling; NULL: the argmax) as
- * it supplies the actions of macm_world_rollout: the device draws nothing and takes no logarithm, and
+ * it supplies the actions of macm_world_rollout, or has the launch draw it (macm_sample_config, below:
+ * only where the noise comes from changes, the action rule above stays word for word);
  * the learner recomputes log-probabilities from the stored logits.
  *   params: device float32, 16-byte aligned, row-major [in][out]:
  *           W1[in_dim][hidden], b1[hidden], (W2[hidden][hidden], b2[hidden] if n_hidden == 2),
@@ -531,6 +532,64 @@ int macm_world_rollout_policy(macm_world* w, uint8_t* actions, int32_t n_steps, 
                               const macm_outputs* out, void* stream);
 int macm_world_rollout_policy_traj(macm_world* w, uint8_t* actions, int32_t n_steps, const float* noise,
                                    float* logits, const macm_outputs* traj, void* stream);
+
+/*
+ * In-launch action sampling: the policy draws its own Gumbel noise from a counter-based generator, so
+ * that sampling from softmax(logits) needs no [n_steps, E, N, 9] noise tensor, and the noise of a
+ * decision is reproducible from (seed, decision index, env, agent, head) however the steps are cut
+ * into launches. For decision index d (uint64), flat row r = e * n_agents + i (uint32) and head h:
+ *   words   w[0..3] = Philox4x32-10(counter = (r, lo32(d), hi32(d), h), key = (lo32(seed), hi32(seed))),
+ *           the standard generator (multipliers 0xD2511F53 and 0xCD9E8D57, Weyl constants 0x9E3779B9
+ *           and 0xBB67AE85, 10 rounds); word c < 3 belongs to logit 3h + c, word 3 is unused;
+ *   uniform u = ((double)w + 0.5) * 2^-32: exact in float64 and strictly inside (0, 1);
+ *   noise   g = (float)(-log(-log(u))): both logarithms the device library's float64 log, every
+ *           operation rounded once, one final rounding to float32;
+ *   action  z[c] = logits[3h + c] + g, the float32 add and the rule of macm_policy_mlp.
+ * In a rollout the decision taken after step k of a launch (the one noise row k serves) has
+ * d = decision + k, `decision` being the world's counter at the call; a reset env's decision on its
+ * new initial obs has the same d. reserved is 0. Additive: MACM_ABI_VERSION stays 9.
+ */
+typedef struct macm_sample_config {
+  uint64_t seed, decision;
+  int32_t reserved[4];
+} macm_sample_config;
+
+/*
+ * The noise that decisions cfg->decision .. cfg->decision + n_dec - 1 draw for rows r < rows, float32
+ * [n_dec, rows, 9]: what a launch with sampling on adds to its logits, bit for bit, so that a launch
+ * given this buffer as `noise` is its twin. words: the generator's raw output, uint32 [n_dec, rows, 3, 4]
+ * (head h, word q at [.., h, q]), or NULL.
+ * MACM_E_INVALID, nothing launched: cfg NULL, reserved != 0, n_dec < 0, rows < 0 or rows > 2^32 (r is a
+ * 32-bit word), noise NULL. n_dec = 0 or rows = 0 writes nothing.
+ */
+int macm_policy_noise(const macm_sample_config* cfg, int64_t n_dec, int64_t rows, float* noise, uint32_t* words,
+                      void* stream);
+
+/*
+ * macm_policy_flock with the draw inside: row r decides at decision cfg->decision, with the bits of
+ * macm_policy_flock given macm_policy_noise(cfg, 1, rows). The first actions of a sampled closed loop
+ * (decision 0, the world's sampling then starting at decision 1), and what the per-step loop calls.
+ * MACM_E_INVALID, nothing launched: as macm_policy_flock, and cfg NULL, reserved != 0, rows > 2^32.
+ */
+int macm_policy_flock_sampled(const macm_policy_mlp* p, const void* obs, int32_t obs_f64, int64_t rows,
+                              const macm_sample_config* cfg, uint8_t* actions, float* logits, void* stream);
+
+/*
+ * Sampling as a property of the world, like autoreset; off at creation. While it is on,
+ * macm_world_rollout_policy / _traj / _value / _value_traj called with noise == NULL draw: the decision
+ * after step k uses d = decision + k, and a call that launched advances the world's host-side
+ * `decision` by n_steps (no synchronisation). One launch on the wave path, whose kernels are
+ * instantiations of their own; on the other paths the per-step loop calls the sampled one-shot kernel
+ * with d = decision + k, which gives the same draws. A call with noise given while sampling is on
+ * returns MACM_E_INVALID, and nothing is launched. cfg NULL turns sampling off: everything is as
+ * before, and noise == NULL is the argmax again.
+ * MACM_E_INVALID, nothing changed: a NULL world, reserved != 0. MACM_E_UNSUPPORTED: a continuous-action
+ * world.
+ * macm_world_get_sampling: 1 with sampling on, *cfg_out the seed and the decision the next launch
+ * starts at; 0 with sampling off, *cfg_out zeroed; MACM_E_INVALID for a NULL argument.
+ */
+int macm_world_set_sampling(macm_world* w, const macm_sample_config* cfg);
+int macm_world_get_sampling(macm_world* w, macm_sample_config* cfg_out);
 
 /*
  * A critic beside the actor: a second float32 MLP over the same obs row, with a trunk of its own and

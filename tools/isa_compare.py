@@ -8,7 +8,8 @@
 A plain diff of the .isa files stops being readable once a translation unit gains a kernel: the
 local labels carry the function's index within the unit (.LBB12_3, .Lfunc_end12), so every kernel
 behind the new one differs in every label. Here each unit's .s is cut into its functions (from the
-symbol's label to its .Lfunc_end), comments dropped and the index taken out of the labels; per unit:
+symbol's label to its .Lfunc_end), comments dropped and the index taken out of the labels (the long
+branches' .Lpost_getpcN, numbered through the unit, likewise); per unit:
 how many of A's kernels are instruction for instruction the same in B, which changed, which are gone
 and how many B adds. Exit status 1 when a kernel of A changed or is gone."""
 import glob
@@ -31,7 +32,8 @@ def functions(path):
         if re.match(r"^\.Lfunc_end", line) or re.match(r"^\s*\.amdgpu_metadata", line):
             cur = None
         if cur:
-            out[cur].append(re.sub(r"\.LBB\d+_", ".LBB_", line))
+            # (.Lpost_getpcN, the label of a long branch's s_getpc, counts through the whole unit as well)
+            out[cur].append(re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", re.sub(r"\.LBB\d+_", ".LBB_", line)))
     return out
 
 

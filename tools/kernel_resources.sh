@@ -3,7 +3,8 @@
 # (compiler remarks), one line per kernel: unit kernel VGPRs AGPRs scratch waves/SIMD LDS
 #   tools/kernel_resources.sh <dir holding csrc/>   (diff two trees to see what a change costs)
 # The policy and critic kernels are among them: the ObsPol / ObsPolV instantiations of the two rollout
-# units, policy.hip's policy_flock_kernel, value_flock_kernel and gae_kernel, and policy_grad.hip's
+# units and their sampled siblings ObsPolS / ObsPolVS, policy.hip's policy_flock_kernel,
+# policy_flock_sampled_kernel, policy_noise_kernel, value_flock_kernel and gae_kernel, and policy_grad.hip's
 # mlp_grad_kernel, mlp_ppo_grad_kernel and mlp_ppo_grad_rows_kernel (one wave per block: waves per CU =
 # 4 x waves/SIMD) and mlp_grad_reduce_kernel, and ppo_loss.hip's policy_logp_kernel, ppo_loss_kernel,
 # ppo_stats_kernel, adv_sum_kernel and adv_finish_kernel, and ppo_adam.hip's ppo_adam_kernel (one workgroup).
