@@ -363,11 +363,17 @@ int mlp_check(const std::string& noun, const M* m) {
 }
 
 // A macm_sample_config as the kernels can take it, over `rows` rows: the flat row is a 32-bit counter word
-inline int sample_check(const macm_sample_config* cfg, int64_t rows) {
+// starting at the job's row first_row (0: the entry points without _at)
+inline int sample_check(const macm_sample_config* cfg, int64_t rows, int64_t first_row = 0) {
+  constexpr int64_t kRowsEnd = (int64_t)1 << 32;
   if (!cfg) return fail(MACM_E_INVALID, "sampling: cfg is NULL");
   for (int i = 0; i < 4; ++i)
     if (cfg->reserved[i] != 0) return fail(MACM_E_INVALID, "sampling: reserved must be 0");
   if (rows < 0) return fail(MACM_E_INVALID, "sampling: rows must be >= 0");
-  if (rows > (int64_t)1 << 32) return fail(MACM_E_INVALID, "sampling: rows must be <= 2^32 (the row is a 32-bit counter word)");
+  if (rows > kRowsEnd) return fail(MACM_E_INVALID, "sampling: rows must be <= 2^32 (the row is a 32-bit counter word)");
+  if (first_row < 0) return fail(MACM_E_INVALID, "sampling: first_row must be >= 0");
+  if (first_row > kRowsEnd || first_row + rows > kRowsEnd)  // (first_row <= 2^32 first: the sum cannot overflow)
+    return fail(MACM_E_INVALID, "sampling: first_row + rows must be <= 2^32 (the row is a 32-bit counter word): first_row " +
+                                    std::to_string(first_row) + ", rows " + std::to_string(rows));
   return MACM_OK;
 }

@@ -30,25 +30,37 @@ int macm_policy_flock(const macm_policy_mlp* p, const void* obs, int32_t obs_f64
   return MACM_OK;
 }
 
-int macm_policy_noise(const macm_sample_config* cfg, int64_t n_dec, int64_t rows, float* noise, uint32_t* words,
-                      void* stream) {
-  if (const int rc = sample_check(cfg, rows)) return rc;
+int macm_policy_noise_at(const macm_sample_config* cfg, int64_t first_row, int64_t n_dec, int64_t rows, float* noise,
+                         uint32_t* words, void* stream) {
+  if (const int rc = sample_check(cfg, rows, first_row)) return rc;
   if (n_dec < 0) return fail(MACM_E_INVALID, "sampling: n_dec must be >= 0");
   if (!noise) return fail(MACM_E_INVALID, "sampling: noise is NULL");
-  HIP_TRY(launch_policy_noise(SampleArgs{cfg->seed, cfg->decision}, n_dec, rows, noise, words, (hipStream_t)stream));
+  HIP_TRY(launch_policy_noise(SampleArgs{cfg->seed, cfg->decision, (uint32_t)first_row}, n_dec, rows, noise, words,
+                              (hipStream_t)stream));
+  return MACM_OK;
+}
+
+int macm_policy_noise(const macm_sample_config* cfg, int64_t n_dec, int64_t rows, float* noise, uint32_t* words,
+                      void* stream) {
+  return macm_policy_noise_at(cfg, 0, n_dec, rows, noise, words, stream);
+}
+
+int macm_policy_flock_sampled_at(const macm_policy_mlp* p, const void* obs, int32_t obs_f64, int64_t first_row,
+                                 int64_t rows, const macm_sample_config* cfg, uint8_t* actions, float* logits,
+                                 void* stream) {
+  if (!p) return fail(MACM_E_INVALID, "policy is NULL");
+  if (const int rc = mlp_check("policy", p)) return rc;
+  if (!obs || !actions) return fail(MACM_E_INVALID, "obs/actions is NULL");
+  if (const int rc = sample_check(cfg, rows, first_row)) return rc;
+  const PolicyArgs M{p->params, nullptr, logits, p->hidden, p->n_hidden};
+  HIP_TRY(launch_policy_flock_sampled(M, SampleArgs{cfg->seed, cfg->decision, (uint32_t)first_row}, obs, obs_f64 != 0,
+                                      p->in_dim, rows, actions, (hipStream_t)stream));
   return MACM_OK;
 }
 
 int macm_policy_flock_sampled(const macm_policy_mlp* p, const void* obs, int32_t obs_f64, int64_t rows,
                               const macm_sample_config* cfg, uint8_t* actions, float* logits, void* stream) {
-  if (!p) return fail(MACM_E_INVALID, "policy is NULL");
-  if (const int rc = mlp_check("policy", p)) return rc;
-  if (!obs || !actions) return fail(MACM_E_INVALID, "obs/actions is NULL");
-  if (const int rc = sample_check(cfg, rows)) return rc;
-  const PolicyArgs M{p->params, nullptr, logits, p->hidden, p->n_hidden};
-  HIP_TRY(launch_policy_flock_sampled(M, SampleArgs{cfg->seed, cfg->decision}, obs, obs_f64 != 0, p->in_dim, rows, actions,
-                                      (hipStream_t)stream));
-  return MACM_OK;
+  return macm_policy_flock_sampled_at(p, obs, obs_f64, 0, rows, cfg, actions, logits, stream);
 }
 
 int macm_value_flock(const macm_value_mlp* c, const void* obs, int32_t obs_f64, int64_t rows, float* values,

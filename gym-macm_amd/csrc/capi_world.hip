@@ -26,7 +26,7 @@ struct macm_world {
   macm_value_mlp critic{0, 0, 0, 0, nullptr};  // macm_world_set_critic: likewise
   // macm_world_set_sampling: the policy rollouts draw their own noise; sample.decision is the next launch's first
   bool sampling = false;
-  SampleArgs sample{0, 0};
+  SampleArgs sample{0, 0, 0};
   uint32_t* hstat = nullptr;  // host-mapped status word (B.host_status is its device alias)
   unsigned long long* bad = nullptr;  // validate_actions: first failing row (device scratch)
   // workgroup-path rollouts: env slices on streams of their own (created on first use)
@@ -702,8 +702,8 @@ static int world_rollout(macm_world* w, const void* actions, int n_steps, const 
       if (M.logits && traj) M.logits += (size_t)k * rows * kPolicyLogits;
       unsigned char* const next = const_cast<unsigned char*>(act_k) + (traj ? rows * 3 : 0);
       if (smp)  // the same draws as the wave path's launch
-        HIP_TRY(launch_policy_flock_sampled(M, SampleArgs{smp->seed, smp->decision + (unsigned long long)k}, ok.obs,
-                                            w->cfg.obs_f64 != 0, obs_dim(w->cfg), rows, next, s));
+        HIP_TRY(launch_policy_flock_sampled(M, SampleArgs{smp->seed, smp->decision + (unsigned long long)k, smp->row0},
+                                            ok.obs, w->cfg.obs_f64 != 0, obs_dim(w->cfg), rows, next, s));
       else
         HIP_TRY(launch_policy_flock(M, ok.obs, w->cfg.obs_f64 != 0, obs_dim(w->cfg), rows, next, s));
     }
@@ -751,20 +751,31 @@ int macm_world_set_policy(macm_world* w, const macm_policy_mlp* p) {
                        w ? &w->policy : nullptr);
 }
 
-// macm_world_set_sampling / _get_sampling: the draw as a property of the world (cfg NULL: off)
-int macm_world_set_sampling(macm_world* w, const macm_sample_config* cfg) {
+// macm_world_set_sampling / _at / _get_sampling / _get_sampling_row: the draw as a property of the world
+// (cfg NULL: off); first_row: the job's row of the world's row 0 (a shard's env_offset * n_agents)
+int macm_world_set_sampling_at(macm_world* w, const macm_sample_config* cfg, int64_t first_row) {
   if (!w) return fail(MACM_E_INVALID, "world is NULL");
   if (!cfg) {
     w->sampling = false;
-    w->sample = SampleArgs{0, 0};
+    w->sample = SampleArgs{0, 0, 0};
     return MACM_OK;
   }
-  if (const int rc = sample_check(cfg, (int64_t)w->P.n_envs * w->P.n_agents)) return rc;
+  if (const int rc = sample_check(cfg, (int64_t)w->P.n_envs * w->P.n_agents, first_row)) return rc;
   if (w->cfg.action_mode != MACM_ACTION_DISCRETE)
     return fail(MACM_E_UNSUPPORTED, "sampling: the MLP policy acts in discrete mode (MultiDiscrete([3, 3, 3]))");
   w->sampling = true;
-  w->sample = SampleArgs{cfg->seed, cfg->decision};
+  w->sample = SampleArgs{cfg->seed, cfg->decision, (uint32_t)first_row};
   return MACM_OK;
+}
+
+int macm_world_set_sampling(macm_world* w, const macm_sample_config* cfg) {
+  return macm_world_set_sampling_at(w, cfg, 0);
+}
+
+int macm_world_get_sampling_row(macm_world* w, int64_t* first_row) {
+  if (!w || !first_row) return fail(MACM_E_INVALID, "world/first_row is NULL");
+  *first_row = (int64_t)w->sample.row0;  // exact: a world has rows, so first_row < 2^32 was required
+  return w->sampling ? 1 : 0;
 }
 
 int macm_world_get_sampling(macm_world* w, macm_sample_config* cfg_out) {

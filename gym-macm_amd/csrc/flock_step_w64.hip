@@ -2782,8 +2782,8 @@ struct ObsPol {};
 template <typename OT>
 struct ObsPolV {};
 // ... and of a world with sampling on (macm_world_set_sampling): ObsPolS / ObsPolVS, the ObsPol / ObsPolV
-// kernels with the draw of policy_sample.hpp where the noise is read; their argument grows by the seed
-// and the launch's first decision index after the fields before. New tags, so that the kernels above
+// kernels with the draw of policy_sample.hpp where the noise is read; their argument grows by the seed,
+// the launch's first decision index and the job's row of the world's row 0 after the fields before. New tags, so that the kernels above
 // keep their names and their code.
 template <typename OT>
 struct ObsPolS {};
@@ -2866,15 +2866,15 @@ __device__ __forceinline__ void policy_act_row(const PolicyArgs& M, int od, cons
   policy_mlp_row<OT>(M, od, obs + row * od, M.noise ? M.noise + (k * EN + row) * kPolicyLogits : nullptr,
                      pol_out + row * 3, M.logits ? M.logits + (kr * EN + row) * kPolicyLogits : nullptr);
 }
-// ... of a sampled rollout: the row draws at decision S.decision + k. The row is the env's, not the
-// wave's: rollout_sched reorders the waves.
+// ... of a sampled rollout: the row draws at decision S.decision + k, as the job's row S.row0 + row. The
+// row is the env's, not the wave's: rollout_sched reorders the waves.
 template <typename OT>
 __device__ __forceinline__ void policy_sample_row(const PolicyArgs& M, const SampleArgs& S, int od,
                                                   const OT* __restrict__ obs, size_t row, size_t k, size_t kr, size_t EN,
                                                   uint8_t* __restrict__ pol_out) {
   policy_mlp_row<OT, true>(M, od, obs + row * od, nullptr, pol_out + row * 3,
                            M.logits ? M.logits + (kr * EN + row) * kPolicyLogits : nullptr,
-                           SampleDraw{S.seed, S.decision + k, (uint32_t)row});
+                           SampleDraw{S.seed, S.decision + k, S.row0 + (uint32_t)row});
 }
 // Carried Flock rollouts (CARRY) only: this bit of RolloutArgs::cur is MACM_DEBUG_ROLLOUT_RELOAD, every
 // step loads its state and waits for the stores of the step before, as a rollout without the carry.

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void policy_flock_sampled_kernel(PolicyArgs M,
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows) return;
   policy_mlp_row<OT, true>(M, od, obs + i * od, nullptr, act + i * 3, M.logits ? M.logits + i * kPolicyLogits : nullptr,
-                           SampleDraw{S.seed, S.decision, (uint32_t)i});
+                           SampleDraw{S.seed, S.decision, S.row0 + (uint32_t)i});
 }
 
 hipError_t launch_policy_flock_sampled(const PolicyArgs& M, const SampleArgs& S, const void* obs, bool obs_f64, int od,
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void policy_noise_kernel(SampleArgs S, long lo
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows) return;
   for (long long j = blockIdx.y; j < n_dec; j += gridDim.y) {
-    const SampleDraw sd{S.seed, S.decision + (unsigned long long)j, (uint32_t)i};
+    const SampleDraw sd{S.seed, S.decision + (unsigned long long)j, S.row0 + (uint32_t)i};
     const size_t at = (size_t)j * (size_t)rows + (size_t)i;
 #pragma unroll
     for (int h = 0; h < 3; ++h) {

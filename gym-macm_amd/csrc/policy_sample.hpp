@@ -7,8 +7,10 @@
 // given macm_policy_noise's output, as ppo_row.hpp is one text for the loss.
 //
 // The definition:
-//   words   w[0..3] = Philox4x32-10(counter = (r, lo32(d), hi32(d), h), key = (lo32(seed), hi32(seed)));
-//           word c < 3 belongs to logit 3h + c, word 3 is unused
+//   words   w[0..3] = Philox4x32-10(counter = (first_row + r, lo32(d), hi32(d), h), key = (lo32(seed), hi32(seed)));
+//           word c < 3 belongs to logit 3h + c, word 3 is unused; r is the flat row of the call or world,
+//           first_row the job's row of its row 0 (0 unless the caller names one: the _at entry points), so that
+//           a shard of a job draws the job's rows; first_row + rows <= 2^32, the sum never wraps
 //   uniform u = ((double)w + 0.5) * 2^-32: exact in float64 and strictly inside (0, 1)
 //   noise   g = (float)(-log(-log(u))), both logarithms the device library's float64 log, every
 //           operation rounded once (-ffp-contract=off), one final rounding to float32
@@ -23,9 +25,10 @@ namespace macm {
 struct SampleArgs {
   unsigned long long seed;
   unsigned long long decision;  // d of the launch's first decision
+  uint32_t row0;                // first_row: the job's row of the call's or world's row 0 (a shard's e0 * N)
 };
 
-// One row's draw: the key, the decision index and the flat row r = e * N + i
+// One row's draw: the key, the decision index and the job's flat row first_row + r, r = e * N + i
 struct SampleDraw {
   unsigned long long seed;
   unsigned long long d;

@@ -207,7 +207,7 @@ struct RolloutArArgs<ObsPolV<OT>> : RolloutArArgs<ObsPol<OT>> {
   ValueArgs val;  // values [E, N] or [K + 1, E, N], boot [E, N] or [K, E, N] with A.traj
 };
 
-// a world with sampling on (ObsPolS / ObsPolVS): the draw's two words follow
+// a world with sampling on (ObsPolS / ObsPolVS): the draw's seed, first decision and first row follow
 template <typename OT>
 struct RolloutArArgs<ObsPolS<OT>> : RolloutArArgs<ObsPol<OT>> {
   SampleArgs smp;  // the decision after step k draws at smp.decision + k (pol.noise is not read)

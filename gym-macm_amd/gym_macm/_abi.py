@@ -296,6 +296,12 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p]),
     "macm_world_set_sampling": (c_int, [c_void_p, POINTER(MacmSampleConfig)]),
     "macm_world_get_sampling": (c_int, [c_void_p, POINTER(MacmSampleConfig)]),
+    # ... with first_row (int64): the job's row of the call's or world's row 0
+    "macm_policy_noise_at": (c_int, [POINTER(MacmSampleConfig), c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "macm_policy_flock_sampled_at": (c_int, [POINTER(MacmPolicyMlp), c_void_p, c_int32, c_int64, c_int64,
+                                             POINTER(MacmSampleConfig), c_void_p, c_void_p, c_void_p]),
+    "macm_world_set_sampling_at": (c_int, [c_void_p, POINTER(MacmSampleConfig), c_int64]),
+    "macm_world_get_sampling_row": (c_int, [c_void_p, POINTER(c_int64)]),
     "macm_value_flock": (c_int, [POINTER(MacmValueMlp), c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
     "macm_world_set_critic": (c_int, [c_void_p, POINTER(MacmValueMlp)]),
     "macm_world_rollout_policy_value": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -5,7 +5,9 @@ SURVEY.md §2). Its envs are fully independent, so the MI355X layout is weak
 scaling with no data-path collective: rank r owns the contiguous global env ids
 [r*E, (r+1)*E), and because every env is seeded by its GLOBAL id (env e ==
 Flock after random.seed(seed + e)) its trajectory is identical whatever the
-number of ranks. The only collectives are one small all-reduce of counters after
+number of ranks; a policy that samples inside the launch draws by the job's row
+(FlockVec.set_sampling: first_row = env_offset * N), so that holds for sampled rollouts too
+(tests/test_gpu_rollout_shards.py). The only collectives are one small all-reduce of counters after
 a measurement window and one all-gather of the per-env reward sums (RCCL over
 xGMI when backend="nccl", gloo in CPU tests).
 """

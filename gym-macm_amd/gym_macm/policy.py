@@ -1,7 +1,7 @@
 """A learned policy as the actor of Flock's closed loop: a float32 MLP over every agent's obs row.
 
     pol = MlpPolicy.from_linear_layers([net.l1, net.l2, net.head], device="cuda:0")
-    acts[0] = pol.act(vec.obs, seed=seed, decision=0)   # the first actions, uint8 [E, N, 3], sampled
+    acts[0] = pol.act(vec.obs, seed=seed, decision=0, first_row=vec.first_row)   # the first actions, uint8 [E, N, 3], sampled
     vec.set_policy(pol); vec.set_sampling(seed, decision=1)
     out = vec.rollout_policy(acts, 128, trajectory=True)   # one launch on the wave path; it draws its own noise
 
@@ -11,7 +11,8 @@ at ``logits[3h + c]``), ``action[h] = argmax_c(logits[3h + c] + noise[3h + c])``
 ties. Gumbel noise samples from the softmax; None is the argmax. A world with sampling on
 (``set_sampling``) and ``act(seed=, decision=)`` draw it inside the launch from a counter-based generator
 (macm_sample_config: Philox4x32-10 over (seed, decision index, row, head), g = -log(-log(u)) in float64),
-reproducible however the steps are cut into launches; ``gumbel_noise`` gives the same numbers as a tensor
+reproducible however the steps are cut into launches and, the row being the job's (``first_row``: a shard's
+``env_offset * N``), however the envs are split over ranks; ``gumbel_noise`` gives the same numbers as a tensor
 for a caller who wants to pass ``noise`` explicitly. The learner recomputes log-probabilities from the
 stored logits.
 
@@ -218,11 +219,13 @@ class MlpPolicy(_Mlp):
         return logits
 
     def act(self, obs: torch.Tensor, noise: torch.Tensor = None, logits: torch.Tensor = None,
-            out: torch.Tensor = None, seed: int = None, decision: int = 0) -> torch.Tensor:
+            out: torch.Tensor = None, seed: int = None, decision: int = 0, first_row: int = 0) -> torch.Tensor:
         """The policy's actions (uint8 [..., 3]) for obs [..., in_dim] (macm_policy_flock); noise and
         logits: float32 [..., 9] or None (logits is written). With ``seed`` the launch draws the noise itself
-        (macm_policy_flock_sampled): flat row r of obs at decision index ``decision``, the numbers of
-        ``gumbel_noise(seed, decision, 1, obs.shape[:-1])``; ``noise`` must then be None."""
+        (macm_policy_flock_sampled_at): flat row r of obs at decision index ``decision``, as the job's row
+        ``first_row + r`` (a shard's obs: ``FlockVec.first_row``), the numbers of
+        ``gumbel_noise(seed, decision, 1, obs.shape[:-1], first_row=first_row)``; ``noise`` must then be None.
+        ``first_row`` is only meaningful with ``seed``."""
         if obs.device != self.device or not obs.is_contiguous() or obs.dtype not in (torch.float32, torch.float64):
             raise ValueError("obs must be a contiguous float32/float64 tensor on the policy's device")
         if obs.shape[-1] != self.in_dim:
@@ -239,15 +242,19 @@ class MlpPolicy(_Mlp):
             raise ValueError(f"out must be a contiguous uint8 {lead + (3,)} tensor on the policy's device")
         p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         L = _abi.lib()
+        if seed is None and first_row != 0:
+            raise ValueError("first_row names the rows of the draw: it needs seed")
         if seed is not None:
             if noise is not None:
                 raise ValueError("noise and seed exclude each other: with seed the launch draws its own noise")
             cfg = sample_config(seed, decision)
+            first_row = sample_first_row(first_row)
             with torch.cuda.device(self.device):
-                _abi.check(L.macm_policy_flock_sampled(ctypes.byref(self._struct), p(obs),
-                                                       1 if obs.dtype == torch.float64 else 0, obs.numel() // self.in_dim,
-                                                       ctypes.byref(cfg), p(out), p(logits), _stream(obs)),
-                           "macm_policy_flock_sampled")
+                _abi.check(L.macm_policy_flock_sampled_at(ctypes.byref(self._struct), p(obs),
+                                                          1 if obs.dtype == torch.float64 else 0, first_row,
+                                                          obs.numel() // self.in_dim, ctypes.byref(cfg), p(out), p(logits),
+                                                          _stream(obs)),
+                           "macm_policy_flock_sampled_at")
             return out
         with torch.cuda.device(self.device):
             _abi.check(L.macm_policy_flock(ctypes.byref(self._struct), p(obs), 1 if obs.dtype == torch.float64 else 0,
@@ -327,12 +334,24 @@ def sample_config(seed: int, decision: int = 0) -> "_abi.MacmSampleConfig":
     return _abi.MacmSampleConfig(seed, decision, (ctypes.c_int32 * 4)(0, 0, 0, 0))
 
 
-def gumbel_noise(seed: int, decision: int, n_dec: int, rows_shape, device=None, words: bool = False):
+def sample_first_row(first_row: int) -> int:
+    """first_row as the C-ABI takes it (an int64 that ctypes would truncate silently); ValueError outside
+    [0, 2**32]. The library checks first_row + rows <= 2**32."""
+    first_row = int(first_row)
+    if not (0 <= first_row <= 1 << 32):
+        raise ValueError("first_row must be in [0, 2**32]")
+    return first_row
+
+
+def gumbel_noise(seed: int, decision: int, n_dec: int, rows_shape, device=None, words: bool = False,
+                 first_row: int = 0):
     """The Gumbel noise that decisions ``decision .. decision + n_dec - 1`` draw under ``seed`` for the rows of
     ``rows_shape`` (e.g. (E, N); row r is the flat index), float32 [n_dec, *rows_shape, 9], in one launch
-    (macm_policy_noise): what a sampling world adds to its logits, bit for bit, so
+    (macm_policy_noise_at): what a sampling world adds to its logits, bit for bit, so
     ``rollout_policy(noise=gumbel_noise(seed, d, K, (E, N)))`` on a world without sampling is the twin of the
-    launch a world with ``set_sampling(seed, d)`` makes. With ``words`` also the generator's raw output:
+    launch a world with ``set_sampling(seed, d)`` makes. ``first_row``: row r is the job's row ``first_row + r``,
+    so the result is rows [first_row, first_row + rows) of the job's noise (a shard with env_offset e0:
+    ``first_row=e0 * N``, the twin of ``set_sampling(seed, d, first_row=e0 * N)``). With ``words`` also the generator's raw output:
     (noise, words), words int32 [n_dec, *rows_shape, 3, 4] holding the uint32 bits (``.cpu().numpy().view(np.uint32)``)."""
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -345,12 +364,14 @@ def gumbel_noise(seed: int, decision: int, n_dec: int, rows_shape, device=None, 
         rows *= d
     n_dec = int(n_dec)
     cfg = sample_config(seed, decision)
+    first_row = sample_first_row(first_row)
     noise = torch.empty((n_dec,) + shape + (N_LOGITS,), dtype=torch.float32, device=device)
     w = torch.empty((n_dec,) + shape + (3, 4), dtype=torch.int32, device=device) if words else None
     with torch.cuda.device(device):
-        _abi.check(_abi.lib().macm_policy_noise(ctypes.byref(cfg), n_dec, rows, ctypes.c_void_p(noise.data_ptr()),
-                                                ctypes.c_void_p(w.data_ptr()) if words else None, _stream(noise)),
-                   "macm_policy_noise")
+        _abi.check(_abi.lib().macm_policy_noise_at(ctypes.byref(cfg), first_row, n_dec, rows,
+                                                   ctypes.c_void_p(noise.data_ptr()),
+                                                   ctypes.c_void_p(w.data_ptr()) if words else None, _stream(noise)),
+                   "macm_policy_noise_at")
     return (noise, w) if words else noise
 
 

@@ -17,7 +17,8 @@ reset overwrites in the step's outputs, is kept per env in ``final_obs`` / ``fin
 ``seed`` must be >= 0 and every env's seed ``seed + env_offset + e`` must lie in [0, 2**64): the
 C-ABI cannot honour ``random.seed``'s meaning outside it (a negative seed's absolute value, keys of
 three or more words), so the constructor and ``reset`` raise ValueError there (World.reset).
-Shard a job over GPUs by giving each rank its contiguous ``env_offset``.
+Shard a job over GPUs by giving each rank its contiguous ``env_offset``; ``set_sampling`` then draws the
+job's rows (``first_row``), so sampled policy rollouts are those of the whole job too.
 Settings keyword arguments are the reference's (flockSettings, settings.py:110-146).
 Returned tensors are views of buffers reused by the next call.
 """
@@ -131,10 +132,26 @@ class FlockVec(object):
         (World.set_critic)."""
         self.world.set_critic(critic)
 
-    def set_sampling(self, seed, decision: int = 0) -> None:
+    @property
+    def first_row(self) -> int:
+        """The job's flat row of this shard's row 0, ``env_offset * N``: what set_sampling registers by
+        default, and what the first actions take (``pol.act(vec.obs, seed=seed, decision=0,
+        first_row=vec.first_row)``). ValueError where it is negative or row 0 has no 32-bit row word."""
+        row = self.env_offset * self.N
+        if not (0 <= row and row + self.num_envs * self.N <= 1 << 32):
+            raise ValueError(f"env_offset * N = {row} does not name this shard's rows in [0, 2**32): "
+                             "pass an explicit first_row to set_sampling")
+        return row
+
+    def set_sampling(self, seed, decision: int = 0, first_row=None) -> None:
         """Sample the actions of rollout_policy inside the launch (World.set_sampling): no noise tensor,
-        reproducible from (seed, decision index) however the steps are cut into launches. ``seed=None``: off."""
-        self.world.set_sampling(seed, decision)
+        reproducible from (seed, decision index) however the steps are cut into launches and however the job's
+        envs are split over ranks: ``first_row=None`` registers ``env_offset * N``, so every shard draws the
+        whole job's noise for its envs (ValueError where that is negative or does not fit: name a first_row).
+        ``seed=None``: off."""
+        if seed is None:
+            return self.world.set_sampling(None)
+        self.world.set_sampling(seed, decision, self.first_row if first_row is None else first_row)
 
     @property
     def sampling(self):

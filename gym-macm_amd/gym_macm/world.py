@@ -362,19 +362,24 @@ class World:
         _abi.check(self.L.macm_world_set_critic(self.h, ctypes.byref(critic.struct())), "macm_world_set_critic")
         self.critic = critic
 
-    def set_sampling(self, seed, decision: int = 0) -> None:
-        """In-launch action sampling (macm_world_set_sampling; off at creation): while it is on,
+    def set_sampling(self, seed, decision: int = 0, first_row: int = 0) -> None:
+        """In-launch action sampling (macm_world_set_sampling_at; off at creation): while it is on,
         ``rollout_policy(noise=None)`` draws its own Gumbel noise, the decision after step k of a launch
         at decision index ``decision + k``, and each launch advances the world's ``decision`` by its
         n_steps: K = 7 then K = 13 samples exactly what K = 20 does. The numbers are
-        ``gym_macm.policy.gumbel_noise(seed, decision, K, (E, N))``. ``seed=None`` turns it off (None is
-        the argmax again). With sampling on, passing ``noise`` raises MacmError."""
+        ``gym_macm.policy.gumbel_noise(seed, decision, K, (E, N), first_row=first_row)``. ``first_row``: this
+        world's row 0 draws as the job's row ``first_row``; a world that holds envs [e0, e0 + E) of a job names
+        ``e0 * N`` and samples what the whole job samples for them (FlockVec.set_sampling does so from its
+        env_offset). ``first_row + E * N`` must not pass 2**32: MacmError, the registration stays.
+        ``seed=None`` turns it off (None is the argmax again) and clears first_row. With sampling on,
+        passing ``noise`` raises MacmError."""
         if seed is None:
-            _abi.check(self.L.macm_world_set_sampling(self.h, None), "macm_world_set_sampling")
+            _abi.check(self.L.macm_world_set_sampling_at(self.h, None, 0), "macm_world_set_sampling_at")
             return
-        from .policy import sample_config
+        from .policy import sample_config, sample_first_row
         cfg = sample_config(seed, decision)
-        _abi.check(self.L.macm_world_set_sampling(self.h, ctypes.byref(cfg)), "macm_world_set_sampling")
+        _abi.check(self.L.macm_world_set_sampling_at(self.h, ctypes.byref(cfg), sample_first_row(first_row)),
+                   "macm_world_set_sampling_at")
 
     @property
     def sampling(self):
@@ -385,6 +390,16 @@ class World:
         if rc < 0:
             _abi.check(rc, "macm_world_get_sampling")
         return (int(cfg.seed), int(cfg.decision)) if rc == 1 else None
+
+    @property
+    def sampling_first_row(self) -> int:
+        """The job's row that this world's row 0 draws as (set_sampling's first_row; 0 with sampling off;
+        macm_world_get_sampling_row)."""
+        row = ctypes.c_int64(0)
+        rc = self.L.macm_world_get_sampling_row(self.h, ctypes.byref(row))
+        if rc < 0:
+            _abi.check(rc, "macm_world_get_sampling_row")
+        return int(row.value)
 
     def rollout_policy(self, actions: torch.Tensor, n_steps: int, noise: torch.Tensor = None, trajectory: bool = False,
                        traj: dict = None, logits: torch.Tensor = None, values: torch.Tensor = None,

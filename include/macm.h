@@ -537,8 +537,9 @@ int macm_world_rollout_policy_traj(macm_world* w, uint8_t* actions, int32_t n_st
  * In-launch action sampling: the policy draws its own Gumbel noise from a counter-based generator, so
  * that sampling from softmax(logits) needs no [n_steps, E, N, 9] noise tensor, and the noise of a
  * decision is reproducible from (seed, decision index, env, agent, head) however the steps are cut
- * into launches. For decision index d (uint64), flat row r = e * n_agents + i (uint32) and head h:
- *   words   w[0..3] = Philox4x32-10(counter = (r, lo32(d), hi32(d), h), key = (lo32(seed), hi32(seed))),
+ * into launches. For decision index d (uint64), flat row r = e * n_agents + i of the call or world,
+ * the job's row first_row of that row 0 (below; 0 unless named) and head h:
+ *   words   w[0..3] = Philox4x32-10(counter = (first_row + r, lo32(d), hi32(d), h), key = (lo32(seed), hi32(seed))),
  *           the standard generator (multipliers 0xD2511F53 and 0xCD9E8D57, Weyl constants 0x9E3779B9
  *           and 0xBB67AE85, 10 rounds); word c < 3 belongs to logit 3h + c, word 3 is unused;
  *   uniform u = ((double)w + 0.5) * 2^-32: exact in float64 and strictly inside (0, 1);
@@ -548,6 +549,14 @@ int macm_world_rollout_policy_traj(macm_world* w, uint8_t* actions, int32_t n_st
  * In a rollout the decision taken after step k of a launch (the one noise row k serves) has
  * d = decision + k, `decision` being the world's counter at the call; a reset env's decision on its
  * new initial obs has the same d. reserved is 0. Additive: MACM_ABI_VERSION stays 9.
+ *
+ * first_row: the counter's row word is first_row + r, so that a call over some rows of a job, or a world
+ * that holds a shard of its envs, draws what the whole job draws for those rows: the rank whose envs are
+ * [e0, e0 + E) of the job names first_row = e0 * n_agents, and its agent (e, i) then draws as the job's
+ * (e0 + e, i). first_row is in [0, 2^32] and first_row + rows <= 2^32 (for a world rows = E * n_agents):
+ * the word never wraps. The entry points with _at take it; those without are the _at ones with
+ * first_row = 0, in every bit. With one seed and first_row = 0 on every rank, local agent (e, i) of every
+ * rank draws the same noise at every decision.
  */
 typedef struct macm_sample_config {
   uint64_t seed, decision;
@@ -564,6 +573,13 @@ typedef struct macm_sample_config {
  */
 int macm_policy_noise(const macm_sample_config* cfg, int64_t n_dec, int64_t rows, float* noise, uint32_t* words,
                       void* stream);
+/*
+ * ... for the job's rows first_row <= r' < first_row + rows: element [j, r] is the noise of the job's row
+ * first_row + r, so the buffer is rows [first_row, first_row + rows) of the job's macm_policy_noise.
+ * MACM_E_INVALID, nothing launched: as macm_policy_noise, and first_row < 0 or first_row + rows > 2^32.
+ */
+int macm_policy_noise_at(const macm_sample_config* cfg, int64_t first_row, int64_t n_dec, int64_t rows, float* noise,
+                         uint32_t* words, void* stream);
 
 /*
  * macm_policy_flock with the draw inside: row r decides at decision cfg->decision, with the bits of
@@ -573,6 +589,15 @@ int macm_policy_noise(const macm_sample_config* cfg, int64_t n_dec, int64_t rows
  */
 int macm_policy_flock_sampled(const macm_policy_mlp* p, const void* obs, int32_t obs_f64, int64_t rows,
                               const macm_sample_config* cfg, uint8_t* actions, float* logits, void* stream);
+/*
+ * ... with row r of obs drawing as the job's row first_row + r: the first actions of a shard's closed loop,
+ * with the bits of macm_policy_flock given macm_policy_noise_at(cfg, first_row, 1, rows).
+ * MACM_E_INVALID, nothing launched: as macm_policy_flock_sampled, and first_row < 0 or
+ * first_row + rows > 2^32.
+ */
+int macm_policy_flock_sampled_at(const macm_policy_mlp* p, const void* obs, int32_t obs_f64, int64_t first_row,
+                                 int64_t rows, const macm_sample_config* cfg, uint8_t* actions, float* logits,
+                                 void* stream);
 
 /*
  * Sampling as a property of the world, like autoreset; off at creation. While it is on,
@@ -587,9 +612,18 @@ int macm_policy_flock_sampled(const macm_policy_mlp* p, const void* obs, int32_t
  * world.
  * macm_world_get_sampling: 1 with sampling on, *cfg_out the seed and the decision the next launch
  * starts at; 0 with sampling off, *cfg_out zeroed; MACM_E_INVALID for a NULL argument.
+ * macm_world_set_sampling_at: the world's row 0 draws as the job's row first_row (a world created with
+ * env_offset e0 as a shard of a job: e0 * n_agents), on every path and in every policy rollout, so that
+ * the shard's sampled launches have the bits of the whole job's for its envs. Also MACM_E_INVALID, nothing
+ * changed (an earlier registration stays): first_row < 0, first_row + E * n_agents > 2^32. cfg NULL
+ * clears first_row to 0 with the rest. macm_world_set_sampling is this with first_row = 0.
+ * macm_world_get_sampling_row: *first_row as registered (0 with sampling off), the return value that of
+ * macm_world_get_sampling; MACM_E_INVALID for a NULL argument.
  */
 int macm_world_set_sampling(macm_world* w, const macm_sample_config* cfg);
 int macm_world_get_sampling(macm_world* w, macm_sample_config* cfg_out);
+int macm_world_set_sampling_at(macm_world* w, const macm_sample_config* cfg, int64_t first_row);
+int macm_world_get_sampling_row(macm_world* w, int64_t* first_row);
 
 /*
  * A critic beside the actor: a second float32 MLP over the same obs row, with a trunk of its own and

@@ -2,8 +2,8 @@
 definition and not from the kernel (tests/ only): the reference that macm_policy_noise,
 macm_policy_flock_sampled and the sampled rollouts are compared with.
 
-    words   w[0..3] = Philox4x32-10(counter = (r, lo32(d), hi32(d), h), key = (lo32(seed), hi32(seed)))
-            word c < 3 belongs to logit 3h + c, word 3 is unused
+    words   w[0..3] = Philox4x32-10(counter = (first_row + r, lo32(d), hi32(d), h), key = (lo32(seed), hi32(seed)))
+            word c < 3 belongs to logit 3h + c, word 3 is unused; first_row + rows <= 2**32
     uniform u = (float64(w) + 0.5) * 2**-32          (exact)
     noise   g = float32(-log(-log(u)))               (float64 logs, one final rounding)
 
@@ -47,12 +47,14 @@ def philox(c0, c1, c2, c3, k0, k1):
     return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
 
 
-def words(seed, decision, n_dec, rows):
-    """uint32 [n_dec, rows, 3, 4]: the words of decisions decision .. decision + n_dec - 1, rows r < rows,
-    heads 0..2 (what macm_policy_noise exports)."""
-    seed, decision = int(seed), int(decision)
+def words(seed, decision, n_dec, rows, first_row=0):
+    """uint32 [n_dec, rows, 3, 4]: the words of decisions decision .. decision + n_dec - 1, the job's rows
+    first_row + r for r < rows, heads 0..2 (what macm_policy_noise_at exports)."""
+    seed, decision, first_row = int(seed), int(decision), int(first_row)
+    if not (0 <= first_row and first_row + rows <= 2**32):
+        raise ValueError("first_row + rows must be in [0, 2**32]: the row is a 32-bit counter word")
     d = np.array([(decision + j) & (2**64 - 1) for j in range(n_dec)], dtype=U64).reshape(n_dec, 1, 1)
-    r = np.arange(rows, dtype=U64).reshape(1, rows, 1)
+    r = (U64(first_row) + np.arange(rows, dtype=U64)).reshape(1, rows, 1)
     h = np.arange(3, dtype=U64).reshape(1, 1, 3)
     return philox(r, d & U64(MASK), d >> U64(32), h, U64(seed & MASK), U64(seed >> 32))
 
@@ -73,6 +75,6 @@ def noise_of_words(w):
     return gumbel64(w[..., :3]).astype(np.float32).reshape(w.shape[:-2] + (9,))
 
 
-def noise(seed, decision, n_dec, rows):
-    """float32 [n_dec, rows, 9]: the noise of macm_policy_noise."""
-    return noise_of_words(words(seed, decision, n_dec, rows))
+def noise(seed, decision, n_dec, rows, first_row=0):
+    """float32 [n_dec, rows, 9]: the noise of macm_policy_noise_at (first_row = 0: macm_policy_noise)."""
+    return noise_of_words(words(seed, decision, n_dec, rows, first_row))

@@ -1,7 +1,8 @@
 """The one-shot kernels of the in-launch Gumbel draw: macm_policy_noise against tests/sample_ref.py
 (the words bit for bit, the noise within the bound and under the cap), macm_policy_flock_sampled
-against macm_policy_flock given that noise (bit for bit, every net shape), and the distribution of the
-sampled actions against the softmax of the stored logits."""
+against macm_policy_flock given that noise (bit for bit, every net shape), the _at forms of both at a first_row
+(the job's rows of a shard, up to the last row a 32-bit word names), and the distribution of the sampled
+actions against the softmax of the stored logits."""
 import numpy as np
 import pytest
 import torch
@@ -22,13 +23,19 @@ SEED = 0x1234_5678_9ABC_DEF0  # >= 2**32: both key words are in use
 CARRY = 2**32 - 2             # with n_dec = 4: the decision index crosses the carry into hi32(d)
 
 
-def noise_and_words(seed, decision, n_dec, rows):
-    """macm_policy_noise into guarded buffers; (noise float32 [n_dec, rows, 9], words uint32 [n_dec, rows, 3, 4])"""
+def noise_and_words(seed, decision, n_dec, rows, first_row=None):
+    """macm_policy_noise (first_row given: macm_policy_noise_at) into guarded buffers; (noise float32
+    [n_dec, rows, 9], words uint32 [n_dec, rows, 3, 4])"""
     gn, gw = Guarded((n_dec, rows, 9), torch.float32, DEV), Guarded((n_dec, rows, 3, 4), torch.int32, DEV)
     cfg = sample_config(seed, decision)
     p = lambda t: ctypes.c_void_p(t.data_ptr())
-    _abi.check(_abi.lib().macm_policy_noise(ctypes.byref(cfg), n_dec, rows, p(gn.t), p(gw.t),
-                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "macm_policy_noise")
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if first_row is None:
+        _abi.check(_abi.lib().macm_policy_noise(ctypes.byref(cfg), n_dec, rows, p(gn.t), p(gw.t), stream),
+                   "macm_policy_noise")
+    else:
+        _abi.check(_abi.lib().macm_policy_noise_at(ctypes.byref(cfg), first_row, n_dec, rows, p(gn.t), p(gw.t), stream),
+                   "macm_policy_noise_at")
     torch.cuda.synchronize()
     assert gn.bands_intact() and gw.bands_intact(), "a store outside the noise or the words buffer"
     return gn.t.cpu().numpy(), gw.t.cpu().numpy().view(np.uint32)
@@ -54,6 +61,61 @@ def test_words_bit_for_bit(rows):
     assert n == 0, "on these few elements the device rounds as the reference does"
     # without the words (NULL) the noise is the same
     assert np.array_equal(gumbel_noise(SEED, CARRY, 4, (rows,), DEV).cpu().numpy().view(np.uint32), noise.view(np.uint32))
+
+
+@pytest.mark.parametrize("first_row", [1, 63 * 64, 2**32 - 65], ids=["1", "63x64", "top"])
+def test_words_at_a_first_row_bit_for_bit(first_row):
+    """macm_policy_noise_at: row r draws as the job's row first_row + r, up to the last row a 32-bit word names
+    (first_row + rows = 2**32: the word does not wrap)."""
+    rows = 65
+    noise, words = noise_and_words(SEED, CARRY, 4, rows, first_row)
+    want = S.words(SEED, CARRY, 4, rows, first_row=first_row)
+    assert np.array_equal(words, want), "the words of Philox4x32-10 over (first_row + r, lo32(d), hi32(d), h)"
+    assert not np.array_equal(words, S.words(SEED, CARRY, 4, rows)), "first_row is part of the counter"
+    n, _ = check_noise(noise.reshape(4, rows, 3, 3), S.gumbel64(want[..., :3]))
+    assert n == 0, "on these few elements the device rounds as the reference does"
+    # the Python helper, with and without the words
+    g, w = gumbel_noise(SEED, CARRY, 4, (rows,), DEV, words=True, first_row=first_row)
+    assert np.array_equal(w.cpu().numpy().view(np.uint32), want)
+    assert np.array_equal(g.cpu().numpy().view(np.uint32), noise.view(np.uint32))
+    assert np.array_equal(gumbel_noise(SEED, CARRY, 4, (rows,), DEV, first_row=first_row).cpu().numpy().view(np.uint32),
+                          noise.view(np.uint32))
+    if first_row + rows < 2**32:  # rows [first_row, first_row + rows) of the job's tensor
+        whole = gumbel_noise(SEED, CARRY, 4, (first_row + rows,), DEV)[:, first_row:]
+        assert np.array_equal(whole.cpu().numpy().view(np.uint32), noise.view(np.uint32))
+    # first_row = 0 through the _at entry point is macm_policy_noise
+    n0, w0 = noise_and_words(SEED, CARRY, 4, rows, 0)
+    n1, w1 = noise_and_words(SEED, CARRY, 4, rows)
+    assert np.array_equal(w0, w1) and np.array_equal(n0.view(np.uint32), n1.view(np.uint32))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("first_row", [63 * 64, 2**32 - 257], ids=["63x64", "top"])
+def test_flock_sampled_at_equals_flock_given_the_noise_at(first_row, dtype):
+    """macm_policy_flock_sampled_at against macm_policy_flock given macm_policy_noise_at's rows, bit for bit."""
+    od, rows, d = (4 if dtype == torch.float32 else 6), 257, CARRY + 1
+    pol = seeded_policy(od, 32, 2)
+    g = torch.Generator(device=DEV)
+    g.manual_seed(rows)
+    obs = ((torch.rand((rows, od), device=DEV, generator=g, dtype=torch.float64) * 2 - 1) * 3).to(dtype)
+    noise = gumbel_noise(SEED, d, 1, (rows,), DEV, first_row=first_row)[0]
+    assert np.array_equal(noise.cpu().numpy().view(np.uint32),
+                          S.noise(SEED, d, 1, rows, first_row=first_row)[0].view(np.uint32)), "on these few elements"
+    lg_a, lg_b = Guarded((rows, 9), torch.float32, DEV), Guarded((rows, 9), torch.float32, DEV)
+    act_a, act_b = Guarded((rows, 3), torch.uint8, DEV), Guarded((rows, 3), torch.uint8, DEV)
+    pol.act(obs, noise=noise, logits=lg_a.t, out=act_a.t)
+    pol.act(obs, seed=SEED, decision=d, first_row=first_row, logits=lg_b.t, out=act_b.t)
+    torch.cuda.synchronize()
+    for x in (lg_a, lg_b, act_a, act_b):
+        assert x.bands_intact()
+    assert torch.equal(act_a.t, act_b.t), "the actions of macm_policy_flock given the noise of these rows"
+    assert torch.equal(lg_a.t.view(torch.int32), lg_b.t.view(torch.int32))
+    assert len(torch.unique(act_b.t)) == 3
+    assert not torch.equal(pol.act(obs, seed=SEED, decision=d), act_b.t), "another first_row, another draw"
+    with pytest.raises(ValueError, match="needs seed"):
+        pol.act(obs, first_row=first_row)
+    with pytest.raises(_abi.MacmError, match="first_row"):
+        pol.act(obs, seed=SEED, decision=d, first_row=2**32 - rows + 1)
 
 
 def test_small_seed_and_decision_zero():

@@ -1,9 +1,10 @@
 """The reference of the in-launch Gumbel draw (tests/sample_ref.py) against what it is defined by:
 the generator's known answers, a Python-int implementation, g = -log(-log(u)) evaluated with `decimal`
-at 50 digits, and the distribution of argmax(logits + g). No GPU."""
+at 50 digits, the distribution of argmax(logits + g), and first_row: a shard's rows are the job's. No GPU."""
 import decimal
 
 import numpy as np
+import pytest
 
 import sample_ref as S
 
@@ -36,6 +37,40 @@ def test_words_follow_the_counter_layout():
             for h in range(3):
                 want = S.philox_int((r, d & S.MASK, d >> 32, h), (SEED & S.MASK, SEED >> 32))
                 assert tuple(int(x) for x in w[j, r, h]) == want
+
+
+def test_first_row_names_the_rows_of_the_job():
+    """words(seed, d, n, rows, first_row=f) is rows [f, f + rows) of the job's words(seed, d, n, f + rows): a
+    shard of a job draws the job's rows. So is the noise."""
+    d0 = 2**32 - 2
+    for f, rows in ((0, 5), (1, 65), (63 * 64, 65), (3 * 33, 2 * 33)):
+        whole = S.words(SEED, d0, 4, f + rows)
+        part = S.words(SEED, d0, 4, rows, first_row=f)
+        assert part.shape == (4, rows, 3, 4) and np.array_equal(part, whole[:, f:]), (f, rows)
+        assert f == 0 or not np.array_equal(part, whole[:, :rows]), "another row, another draw"
+        assert np.array_equal(S.noise(SEED, d0, 4, rows, first_row=f).view(np.uint32),
+                              S.noise(SEED, d0, 4, f + rows)[:, f:].view(np.uint32))
+    assert np.array_equal(S.words(SEED, 3, 2, 7, first_row=0), S.words(SEED, 3, 2, 7))
+
+
+def test_first_row_at_the_top_of_the_range():
+    """first_row = 2**32 - rows: the last rows a 32-bit word can name, against the Python-int generator; the
+    row word does not wrap, and one row more is refused."""
+    rows, d0 = 65, 2**32 - 2
+    f = 2**32 - rows
+    w = S.words(SEED, d0, 4, rows, first_row=f)
+    for j in range(4):
+        d = d0 + j
+        for r in (0, 1, rows - 2, rows - 1):
+            for h in range(3):
+                want = S.philox_int((f + r, d & S.MASK, d >> 32, h), (SEED & S.MASK, SEED >> 32))
+                assert tuple(int(x) for x in w[j, r, h]) == want, (j, r, h)
+    assert (f + rows - 1) == S.MASK
+    assert not np.array_equal(w[:, -1], S.words(SEED, d0, 4, 1)[:, 0]), "row 2**32 - 1 is not row 0"
+    assert S.words(SEED, d0, 1, 0, first_row=2**32).shape == (1, 0, 3, 4)
+    for bad_f, bad_rows in ((f + 1, rows), (-1, rows), (2**32, 1)):
+        with pytest.raises(ValueError, match="first_row"):
+            S.words(SEED, d0, 1, bad_rows, first_row=bad_f)
 
 
 def _exact_g(w: int) -> decimal.Decimal:
