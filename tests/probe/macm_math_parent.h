@@ -1,15 +1,14 @@
+// TEST-ONLY: gym-macm_amd/csrc/macm_math.h as it stood before its f64 forms were rearranged, kept
+// verbatim below this paragraph as the reference of tests/test_math_forms.py and
+// tests/test_gpu_f64_forms.py (tests/probe/math_forms.c includes it under other function names).
+// No product code includes it. Do not edit it to follow the product header.
+//
 // macm_math.h — the f64 elementary functions the step evaluates itself instead of
 // calling the device libm. One source for both sides: the HIP kernels include it, and
 // the host checks (tools/trig_check.c, tools/atan2_check.c) compile the SAME code with
 // gcc -ffp-contract=off and compare it with glibc, which is what the reference's
 // math.cos / math.sin / math.atan2 / np.arctan2 call. Every operation is a single IEEE
-// op (fma only where written), so host and device results are bit-identical. Two places differ
-// between the sides in how they are written, not in what they return: obs_atan2_core's division
-// (macm_div_f32sums: the device writes out the correctly rounded sequence its compiler emits for
-// `/`, less the scaling its operands never need; the host keeps `/`) and macm_pick_const (a
-// select of constants, done with integer masks on the device). tests/test_math_forms.py compares
-// this header with its earlier forms on the host, tests/test_gpu_f64_forms.py and
-// tests/test_gpu_primitives.py the device with the host.
+// op (fma only where written), so host and device results are bit-identical.
 #pragma once
 #include <math.h>
 
@@ -43,63 +42,6 @@ __device__ __forceinline__ double macm_ks(double c) {
 #define MACM_KS(c) (c)
 #define MACM_KS_FN(f, pin) f
 #endif
-
-// v with its sign bit flipped where flip = 0x80000000 (flip = 0: v itself): one integer XOR on the
-// high word. -v is this flip for every double, NaNs and zeros included.
-MACM_MATH_FN double macm_flip_sign(double v, unsigned int flip) {
-  unsigned long long u;
-  __builtin_memcpy(&u, &v, sizeof u);
-  u ^= (unsigned long long)flip << 32;
-  __builtin_memcpy(&v, &u, sizeof u);
-  return v;
-}
-
-// c ? a : b for two constants a and b. On the device a select between literals costs, per 32-bit
-// word, two v_mov_b32 (a v_cndmask_b32 takes its mask from a scalar pair and so no literal) and the
-// v_cndmask_b32; here the lane's mask m = c ? ~0 : 0 is made once and each word is
-// b ^ (m & (a ^ b)): a v_and_b32 and a v_xor_b32 with literal operands. The empty asm keeps the
-// compiler from turning that back into the select. The bits of a or of b, nothing computed.
-MACM_MATH_FN double macm_pick_const(int c, double a, double b) {
-#ifdef __HIPCC__
-  unsigned long long ua, ub;
-  __builtin_memcpy(&ua, &a, sizeof ua);
-  __builtin_memcpy(&ub, &b, sizeof ub);
-  unsigned int m = c ? ~0u : 0u;
-  asm("" : "+v"(m));
-  const unsigned int lo = (unsigned int)ub ^ (m & (unsigned int)(ua ^ ub));
-  const unsigned int hi = (unsigned int)(ub >> 32) ^ (m & (unsigned int)((ua ^ ub) >> 32));
-  const unsigned long long u = ((unsigned long long)hi << 32) | lo;
-  double r;
-  __builtin_memcpy(&r, &u, sizeof r);
-  return r;
-#else
-  return c ? a : b;
-#endif
-}
-
-// num / den for obs_atan2_core's operands: sums and differences of float32-valued doubles, so
-// |den| in [2^-149, 2^130] and num = 0 or |num| in [2^-149, 2^130], |num| <= |den|.
-// Device: the compiler's lowering of an f64 `/` is v_div_scale (both operands) -> v_rcp_f64 -> two
-// Newton steps -> quotient -> residual -> v_div_fmas -> v_div_fixup. For these operands neither
-// v_div_scale engages (no f64 denormal operand, quotient or reciprocal; exponents less than 768
-// apart; a numerator's exponent above 53, and a zero numerator gives a zero quotient scaled or
-// not), so they return their inputs, v_div_fmas is a plain fma and v_div_fixup passes its finite
-// nonzero-denominator result through. What remains is written out below: the same instructions on
-// the same values in the same order, hence the same bits as `/`, which is correctly rounded.
-// den = 0 (only with num = 0: both inputs of obs_atan2 zero) gives a NaN as 0 / 0 does, though not
-// necessarily the same one: obs_atan2_finish replaces it, and no caller uses the core without it.
-// Host: the plain `/` (IEEE, correctly rounded), so host and device stay bit-identical.
-MACM_MATH_FN double macm_div_f32sums(double num, double den) {
-#ifdef __HIPCC__
-  double r = __builtin_amdgcn_rcp(den);
-  r = fma(r, fma(-den, r, 1.0), r);
-  r = fma(r, fma(-den, r, 1.0), r);
-  const double q = num * r;
-  return fma(fma(-den, q, num), r, q);
-#else
-  return num / den;
-#endif
-}
 
 // sin and cos of one argument, |x| < 2^19 * pi/2 (beyond that: the library, see the
 // caller). Cody-Waite reduction x = n*pi/2 + (y0 + y1) with pi/2 split into 33-bit
@@ -194,20 +136,19 @@ MACM_KS_TPL MACM_MATH_FN void macm_sincos_pair(double x, double* s0p, double* c0
   const double cz = ((1.0 - wc) - hz) + z * (z * pc);
   const double ca = wc + (cz - y0 * y1);
   const double cb = wc + (cz - y0 * y1b);
-  // quadrant q: (sin, cos) = (sa, ca) rotated; quadrant q + 1 for x1. The rotation's negations are
-  // sign-bit flips (IEEE negation is exactly that, for every value), taken from q in integer:
-  // sin flips when q & 2, cos when (q + 1) & 2; for q1 = q + 1 the sine's flip is the cosine's of q
-  // and the cosine's, (q + 2) & 2, is the opposite of the sine's of q. The same bits as
-  // `if (q & 2) so = -so` and its three siblings, without a compare and a select for each.
+  // quadrant q: (sin, cos) = (sa, ca) rotated; quadrant q + 1 for x1
   const int odd = q & 1;
-  const double so = odd ? ca : sa, co = odd ? sa : ca;
-  const double so1 = odd ? sb : cb, co1 = odd ? cb : sb;  // ((q + 1) & 1) == !odd
-  const unsigned int fs = ((unsigned int)q << 30) & 0x80000000u;        // q & 2
-  const unsigned int fc = ((unsigned int)(q + 1) << 30) & 0x80000000u;  // (q + 1) & 2
-  *s0p = (x == 0.0) ? x : macm_flip_sign(so, fs);  // sin(-0) = -0
-  *c0p = macm_flip_sign(co, fc);
-  *s1p = macm_flip_sign(so1, fc);
-  *c1p = macm_flip_sign(co1, fs ^ 0x80000000u);
+  double so = odd ? ca : sa, co = odd ? sa : ca;
+  if (q & 2) so = -so;
+  if ((q + 1) & 2) co = -co;
+  const int q1 = q + 1;
+  double so1 = odd ? sb : cb, co1 = odd ? cb : sb;  // (q1 & 1) == !odd
+  if (q1 & 2) so1 = -so1;
+  if ((q1 + 1) & 2) co1 = -co1;
+  *s0p = (x == 0.0) ? x : so;  // sin(-0) = -0
+  *c0p = co;
+  *s1p = so1;
+  *c1p = co1;
 }
 
 // The action trig (mvmnt.py:113-116, combat.py:147): sin/cos of the float32 angle a and
@@ -275,19 +216,8 @@ MACM_KS_TPL MACM_MATH_FN double obs_atan2_core(double ax, double ay) {
   const double mx = swap ? ay : ax, mn = swap ? ax : ay;
   const int r0 = mn < 0.4375 * mx;         // id -1: atan(a) directly
   const int r1 = !r0 && mn < 0.6875 * mx;  // id 0: atan(1/2) + atan((2a-1)/(2+a)); else id 1: pi/4 + ...
-  // (c_a mn - c_b mx) / (c_d mn + c_a mx) with c_a = r1 ? 2 : 1 and c_b = c_d = r0 ? 0 : 1, which the
-  // step used to evaluate as fma(c_a, mn, -(c_b * mx)) / fma(c_d, mn, c_a * mx): two products before
-  // the two fmas. The products only ever give 0, mx or 2 mx, so the zero is selected into the
-  // addend instead and c_a multiplies inside the fma. The same bits for finite mx >= mn >= +0:
-  //   numerator:   c_b * mx is +0 (r0) or mx, exactly what is selected; the fma is the same one
-  //   denominator: fma(c_d, mn, c_a * mx) and fma(c_a, mx, c_d mn) round the same real number
-  //                c_a mx + c_d mn once (c_a * mx and c_d * mn are exact: c_a is 1 or 2, c_d 0 or 1);
-  //                r0: +0 + mx = mx either way (mx > 0 there)
-  // (an exact zero difference is +0 in both forms: round to nearest).
-  const double ca = r1 ? 2.0 : 1.0;
-  const double num = fma(ca, mn, -(r0 ? 0.0 : mx));
-  const double den = fma(ca, mx, r0 ? 0.0 : mn);
-  const double xr = macm_div_f32sums(num, den);
+  const double ca = r1 ? 2.0 : 1.0, cb = r0 ? 0.0 : 1.0, cd = r0 ? 0.0 : 1.0;
+  const double xr = fma(ca, mn, -(cb * mx)) / fma(cd, mn, ca * mx);
   const double z = xr * xr;
   double p = MACM_KS(1.62858201153657823623e-02);
   p = fma(p, z, MACM_KS(-3.65315727442169155270e-02));
@@ -301,16 +231,15 @@ MACM_KS_TPL MACM_MATH_FN double obs_atan2_core(double ax, double ay) {
   p = fma(p, z, MACM_KS(-1.99999999998764832476e-01));
   p = fma(p, z, MACM_KS(3.33333333333329318027e-01));
   const double sz = z * p;
-  const double hi = macm_pick_const(r1, 4.63647609000806093515e-01, 7.85398163397448278999e-01);
-  const double nlo = macm_pick_const(r1, -2.26987774529616870924e-17, -3.06161699786838301793e-17);
-  double r = r0 ? fma(-xr, sz, xr) : hi - (fma(xr, sz, nlo) - xr);
+  const double hi = r1 ? 4.63647609000806093515e-01 : 7.85398163397448278999e-01;
+  const double lo = r1 ? 2.26987774529616870924e-17 : 3.06161699786838301793e-17;
+  double r = r0 ? fma(-xr, sz, xr) : hi - (fma(xr, sz, -lo) - xr);
   if (swap) r = (1.57079632679489655800e+00 - r) + 6.12323399573676603587e-17;
   return r;
 }
 
 MACM_MATH_FN double obs_atan2_finish(double r, double y, double x) {
   if (x < 0.0) r = (3.1415926535897931160e+00 - r) + 1.2246467991473531772e-16;
-  // x = y = 0: the core's r is the NaN of 0 / 0 (on the device, of macm_div_f32sums), replaced here
   if (x == 0.0 && y == 0.0) r = signbit(x) ? 3.1415926535897931160e+00 : 0.0;
   return copysign(r, y);
 }
