@@ -40,7 +40,11 @@ __device__ __forceinline__ void store4(OT* o, double a, double b, double c, doub
 // Both directions share r (|rel| is the same), the ally flag, the mask and atan2's
 // reduction and polynomial (obs_atan2_core of |rel.x|, |rel.y|); each keeps its own
 // rel = other - agent (float32), quadrant, "- angle" and wrap, so every value is bit-identical
-// to evaluating the two slots separately, with half the f64 atan2 work.
+// to evaluating the two slots separately, with half the f64 atan2 work. The reverse direction's
+// p is 0.0 - p1, not -p1: the same bits as wrap_pi(ai - aj) for every pair of angles, equal ones
+// included (+0.0, where a sign flip gave -0.0). A masked slot is sixteen (float64: thirty-two)
+// zero bytes in every writer. tests/test_gpu_tdm_obs_bits.py compares every writer of this file and
+// tdm_obs_snap.hip with a host restatement (tests/tdm_obs_ref.py) on bit patterns.
 // m: both agents alive.
 template <typename OT>
 __device__ __forceinline__ void tdm_obs_pair_m(OT* __restrict__ obs, uint8_t* __restrict__ mask, int S, int i, int j,
@@ -57,7 +61,10 @@ __device__ __forceinline__ void tdm_obs_pair_m(OT* __restrict__ obs, uint8_t* __
     t1 = wrap_pi(obs_atan2_finish(core, (double)ry, (double)rx) - (double)ai);
     t2 = wrap_pi(obs_atan2_finish(core, (double)qy, (double)qx) - (double)aj);
     p1 = wrap_pi((double)aj - (double)ai);
-    p2 = -p1;  // = wrap_pi(ai - aj) exactly: a - b == -(b - a) and the wrap is odd in IEEE arithmetic
+    // = wrap_pi(ai - aj) on bits: a - b == -(b - a) and the wrap is odd in IEEE arithmetic, except
+    // for equal angles, where ai - aj is +0.0 and -p1 would be -0.0; 0.0 - p1 is -p1 for every
+    // other p1 and +0.0 there (one v_add_f64 with a negated operand)
+    p2 = 0.0 - p1;
     ty = tdm_team_nb(TP, j) == tdm_team_nb(TP, i) ? 1.0 : 0.0;
   }
   const size_t s1 = (size_t)i * S + (j - 1), s2 = (size_t)j * S + i;
@@ -171,7 +178,8 @@ __device__ __forceinline__ void tdm_obs_pairs(OT* __restrict__ obs, uint8_t* __r
 // 8 x 496 B = 31 whole lines at N = 32) gets its tiles (R, J > R) in the pair's own direction
 // (row i, slot j - 1), its diagonal tile, and its slots i < 8R, which the tiles (I < R, R)
 // computed in earlier blocks and left in an LDS stage as the finished float32 slot (the same bits
-// the pair form stores). The pair tiles wrote that direction into rows of later blocks as 8-slot
+// the pair form stores: a masked slot is staged as four +0.0f, p as 0.0 - p1). The pair
+// tiles wrote that direction into rows of later blocks as 8-slot
 // runs spread over the whole obs phase, whose lines left L2 partly written (PMC: ~150 B per
 // agent-step of HBM writes above the algorithmic bytes). float32 obs; stage:
 // 512 nb (nb - 1) bytes, nb = N / 8 rounded up (6 KB at N = 32: the wave kernel's dead contact
@@ -222,8 +230,9 @@ __device__ __forceinline__ void tdm_obs_rowblocks(OT* __restrict__ obs, uint8_t*
         const size_t s1 = (size_t)i * S + (j - 1);
         if (obs) store4<OT>(obs + s1 * 4, r, t1, p1, ty);
         if (mk) mk[s1] = m ? 1 : 0;
-        // row j = 8J + b, slot i, as store4 would write it (p2 = -p1 exactly); lanes contiguous
-        stage[soff(J) + 8 * i + b] = make_float4((float)r, (float)t2, (float)(-p1), (float)ty);
+        // row j = 8J + b, slot i, as store4 would write it; lanes contiguous. p2 = 0.0 - p1 as in
+        // tdm_obs_pair_m: +0.0 for a masked slot (p1 = 0.0) and for equal angles, where -p1 is -0.0
+        stage[soff(J) + 8 * i + b] = make_float4((float)r, (float)t2, (float)(0.0 - p1), (float)ty);
       }
     }
     // the diagonal tiles two at a time (lanes 0-27 block R, lanes 32-59 block R + 1, as the pair

@@ -11,8 +11,10 @@
 //
 // Every value is bit-identical to the wave kernel's pair form (tdm_obs.hpp tdm_obs_pair_m): the
 // same float32 rel per direction, the shared atan2 core of |rel| (|xj - xi| == |xi - xj| in IEEE
-// arithmetic), each direction's own quadrant, "- angle" and wrap, p = wrap(aj - ai), r =
-// obs_sqrt<OT> of the same float32 distance.
+// arithmetic), each direction's own quadrant, "- angle" and wrap, r = obs_sqrt<OT> of the same
+// float32 distance. p = wrap(aj - ai) is evaluated per slot here; the pair form derives the reverse
+// direction as 0.0 - p1, which has the same bits (equal angles: +0.0 in both directions). Masked
+// slots are all-zero bits. tests/test_gpu_tdm_obs_bits.py holds both forms to tests/tdm_obs_ref.py.
 #include "flock_common.hpp"
 #include "launch.hpp"
 #include "tdm_obs.hpp"

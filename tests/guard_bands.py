@@ -20,6 +20,11 @@ FLOCK_FIELDS = ("obs", "nbr_id", "reward", "collided", "done")
 TDM_FIELDS = ("obs", "mask", "health", "alive", "done", "winner")
 
 
+def int_view(t):
+    """A float tensor as integers of the same width (its bit patterns); any other tensor as it is."""
+    return t.view({4: torch.int32, 8: torch.int64}[t.element_size()]) if t.is_floating_point() else t
+
+
 class Guarded:
     def __init__(self, shape, dtype, device="cuda:0"):
         self.nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
@@ -87,3 +92,5 @@ class GuardedOutputs:
         for f in self.fields:
             if fields is None or f in fields:
                 assert torch.equal(self.bufs[f].t, twin[f]), f"{ctx}: {f} differs from the twin's"
+                if f == "obs":  # torch.equal on floats takes -0.0 for +0.0: the bit patterns as well
+                    assert torch.equal(int_view(self.bufs[f].t), int_view(twin[f])), f"{ctx}: obs bits differ from the twin's"

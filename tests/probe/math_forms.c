@@ -51,6 +51,11 @@ void forms_parent_atan2_n(const double* y, const double* x, double* out, size_t 
   for (size_t i = 0; i < n; ++i) out[i] = parent_obs_atan2(y[i], x[i]);
 }
 
+/* the current obs_atan2 alone: the atan2 of tests/tdm_obs_ref.py */
+void forms_obs_atan2_n(const double* y, const double* x, double* out, size_t n) {
+  for (size_t i = 0; i < n; ++i) out[i] = obs_atan2(y[i], x[i]);
+}
+
 /* the float32 quantities the step derives from the four doubles: every (k0, k1), cc = 1 and
  * 1/sqrt(2), F = 20 and 16, and the melee-ray offsets (range 2) */
 static int forces_same(const double* p, const double* q) {

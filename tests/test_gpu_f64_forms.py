@@ -30,6 +30,8 @@ from test_math_forms import forms  # noqa: F401  (fixture: both headers built fo
 
 pytestmark = pytest.mark.gpu
 
+from gym_macm._abi import DEBUG_FORCE_SPILL  # noqa: E402
+
 PI32 = np.float32(np.pi)
 
 
@@ -269,3 +271,30 @@ def test_tdm_world_matches_oracle():
 def test_workgroup_flock_world_matches_oracle():
     vec, orc = make_pair(2, [96], seed=19)
     check_rollout(vec, orc, 10, np.random.default_rng(6))
+
+
+# The workgroup step (flock_step_wg.hip) and the spill step (flock_spill.hpp) carry their own copies of
+# write_obs: the polar observation on bits as above. (The cartesian observation calls the device libm's
+# cos / sin, which the host cannot restate bit for bit: it stays at its tolerance.)
+OTHER_WRITERS = {"2x96-workgroup": (2, 96, 0), "2x33-spill": (2, 33, DEBUG_FORCE_SPILL)}
+
+
+@pytest.mark.parametrize("obs_f64", [False, True], ids=["f32", "f64"])
+@pytest.mark.parametrize("name", list(OTHER_WRITERS))
+def test_workgroup_and_spill_observations_are_the_earlier_headers_bits(forms, name, obs_f64):  # noqa: F811
+    E, N, debug = OTHER_WRITERS[name]
+    vec, orc = make_pair(E, [N], seed=19, obs_dtype=torch.float64 if obs_f64 else torch.float32)
+    if debug:
+        vec.world.set_debug(debug)
+    rng = np.random.default_rng(6)
+    for t in range(10):
+        a = rand_actions(rng, E, N)
+        obs, nbr = (o.cpu().numpy() for o in vec.step(torch.from_numpy(a).cuda())[:2])
+        r = orc.step(a)
+        np.testing.assert_array_equal(nbr, r["nbr_id"], err_msg=f"{name} nbr step {t}")
+        o32, o64 = expected_obs(forms, orc.get_state(vec.world.C), r["nbr_id"], vec.targets_idx)
+        same_obs(obs, o64 if obs_f64 else o32, f"{name} step {t}")
+    assert_state_equal(vec.get_state(), orc.get_state(vec.world.C), f"{name} after 10 steps")
+    assert vec.status() == 0
+    if debug:
+        assert vec.spilled() > 0, "no env took the spill step"

@@ -321,8 +321,10 @@ def test_flock_forms_agree_with_the_trajectory_launch(form, N, K):
 # ---- 5. TDM wave path ----------------------------------------------------------------------------------
 def fused_observation(monkeypatch):
     """The loop's steps observe inside the step kernel, as every step of an autoreset rollout does, so
-    that the bits compare: the split observation, step()'s default below 1024 envs, writes +0.0 where
-    the step kernel writes -0.0 into the p of a masked slot (a dead agent's), equal values of other bits."""
+    that the same writer is compared with itself. (When this was written the step kernel's row-block stage
+    wrote -0.0 into the p of a masked slot, a dead agent's, where the split observation, step()'s default
+    below 1024 envs, wrote +0.0; the stage has since been corrected and tests/test_gpu_tdm_obs_bits.py
+    holds every writer to the same bits.)"""
     monkeypatch.setenv("MACM_TDM_SPLIT_OBS", "0")
 
 

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 from guard_bands import Guarded, GuardedOutputs
+from test_gpu_tdm_split import same_tensor  # obs on bit patterns, the rest on values
 from tdm_events_ref import FIXTURES, fixture_actions, fixture_config, replay, run_fixture
 
 pytestmark = pytest.mark.gpu
@@ -48,7 +49,7 @@ def assert_twins(a, b, ctx, outputs=True, counters=True):
     torch.cuda.synchronize()
     if outputs:
         for k in OUT:
-            assert torch.equal(getattr(a, k), getattr(b, k)), f"{ctx}: output {k} differs from the twin's"
+            assert same_tensor(getattr(a, k), getattr(b, k), k), f"{ctx}: output {k} differs from the twin's"
     sa, sb = a.get_state(), b.get_state()
     for k in sa:
         np.testing.assert_array_equal(sa[k], sb[k], err_msg=f"{ctx}: state[{k}]")
@@ -60,7 +61,7 @@ def assert_twins(a, b, ctx, outputs=True, counters=True):
 
 def assert_traj_twins(ta, tb, ctx):
     for k in OUT:
-        assert torch.equal(ta[k], tb[k]), f"{ctx}: trajectory {k} differs from the twin's"
+        assert same_tensor(ta[k], tb[k], k), f"{ctx}: trajectory {k} differs from the twin's"
 
 
 def step_loop(w, acts, reset):

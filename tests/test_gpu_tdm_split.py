@@ -27,9 +27,19 @@ def actions(K, E, N, seed, p_attack=0.5):
     return random_tdm_actions((K, E, N), seed, p_attack)
 
 
+def obs_bits(x):
+    """A float tensor as integers of the same width: torch.equal on floats takes -0.0 for +0.0."""
+    return x.view({4: torch.int32, 8: torch.int64}[x.element_size()]) if x.is_floating_point() else x
+
+
+def same_tensor(x, y, nm):
+    """Equal values, and for the observation equal bit patterns."""
+    return torch.equal(x, y) and (nm != "obs" or torch.equal(obs_bits(x), obs_bits(y)))
+
+
 def same_outputs(a, b, ctx):
     for x, y, nm in zip(a.outputs(), b.outputs(), ("obs", "mask", "health", "alive", "done", "winner")):
-        assert torch.equal(x, y), f"{ctx}: {nm}"
+        assert same_tensor(x, y, nm), f"{ctx}: {nm}"
 
 
 def same_state(a, b, ctx):
@@ -78,7 +88,7 @@ def test_split_equals_fused(monkeypatch, E, teams, kw, debug):
     ta = call(monkeypatch, False, a.rollout_traj, acts[K:2 * K])  # trajectory: chunks 8, 8, 3
     tb = call(monkeypatch, True, b.rollout_traj, acts[K:2 * K])
     for key in ta:
-        assert torch.equal(ta[key], tb[key]), f"trajectory rollout: {key}"
+        assert same_tensor(ta[key], tb[key], key), f"trajectory rollout: {key}"
     same_state(a, b, "trajectory rollout")
     call(monkeypatch, False, a.rollout, acts[2 * K:3 * K + 2])  # overwrite: the last step's outputs
     call(monkeypatch, True, b.rollout, acts[2 * K:3 * K + 2])
@@ -102,7 +112,7 @@ def test_default_form_below_1024_envs(monkeypatch):
     ta = call_env(monkeypatch, FUSED, a.rollout_traj, acts)
     tb = b.rollout_traj(acts)  # default
     for key in ta:
-        assert torch.equal(ta[key], tb[key]), key
+        assert same_tensor(ta[key], tb[key], key), key
     same_state(a, b, "default form")
 
 
@@ -147,7 +157,7 @@ def test_tail_equals_fused(monkeypatch, E, teams, kw, debug, K, workers):
         ta = call_env(monkeypatch, FUSED, a.rollout_traj, acts[r * K:(r + 1) * K])
         tb = call_env(monkeypatch, env, b.rollout_traj, acts[r * K:(r + 1) * K])
         for key in ta:
-            assert torch.equal(ta[key], tb[key]), f"launch {r}: {key}"
+            assert same_tensor(ta[key], tb[key], key), f"launch {r}: {key}"
         same_state(a, b, f"launch {r}")
     assert a.status() == 0 and b.status() == 0
     if debug:
@@ -165,6 +175,6 @@ def test_reserve_then_rollouts(monkeypatch):
         ta = call_env(monkeypatch, FUSED, a.rollout_traj, acts[lo:hi])
         tb = b.rollout_traj(acts[lo:hi])
         for key in ta:
-            assert torch.equal(ta[key], tb[key]), f"steps {lo}..{hi}: {key}"
+            assert same_tensor(ta[key], tb[key], key), f"steps {lo}..{hi}: {key}"
     same_state(a, b, "after the rollouts")
     assert b.launch_flags() & _abi.LAUNCH_TAIL_OBS

@@ -36,6 +36,8 @@ def forms(tmp_path_factory):
     lib.forms_trig_n.restype = S
     lib.forms_parent_atan2_n.argtypes = [P, P, P, S]
     lib.forms_parent_atan2_n.restype = None
+    lib.forms_obs_atan2_n.argtypes = [P, P, P, S]
+    lib.forms_obs_atan2_n.restype = None
     return lib
 
 
