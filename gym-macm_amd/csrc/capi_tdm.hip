@@ -24,6 +24,12 @@ struct macm_tdm {
   // macm_tdm_set_events: the caller's buffer, kept until replaced or cleared (hit_id NULL: none; the
   // steps then launch the kernels without events, the ones they have always launched)
   macm_tdm_events events{nullptr, 0};
+  // macm_tdm_set_policy: the caller's struct (params NULL: none), the teams it acts for, and their agents
+  // as the one-shot kernel's [N] mask on the device (the workgroup path's per-step loop; NULL: every team)
+  macm_tdm_policy policy{0, {0, 0, 0}, nullptr};
+  uint32_t policy_teams = 0;
+  uint8_t* policy_agents = nullptr;
+  bool policy_all = false;
   uint32_t* hstat = nullptr;
   unsigned long long* bad = nullptr;
   int slots_alloc = 0;  // as macm_world
@@ -380,6 +386,64 @@ int macm_tdm_set_events(macm_tdm* w, const macm_tdm_events* ev) {
   return MACM_OK;
 }
 
+// A macm_tdm_policy as the kernels can take it
+static int tdm_policy_check(const macm_tdm_policy* p) {
+  if (p->hidden != 16 && p->hidden != 32) return fail(MACM_E_INVALID, "tdm policy: hidden must be 16 or 32");
+  for (int i = 0; i < 3; ++i)
+    if (p->reserved[i] != 0) return fail(MACM_E_INVALID, "tdm policy: reserved must be 0");
+  if (!p->params) return fail(MACM_E_INVALID, "tdm policy: params is NULL");
+  if (reinterpret_cast<uintptr_t>(p->params) & 15) return fail(MACM_E_INVALID, "tdm policy: params must be 16-byte aligned");
+  return MACM_OK;
+}
+
+int macm_policy_tdm(const macm_tdm_policy* p, const void* obs, const uint8_t* mask, const double* health,
+                    int32_t obs_f64, int32_t n_agents, int64_t rows, const uint8_t* agents, const float* noise,
+                    uint8_t* actions, float* logits, void* stream) {
+  if (!p) return fail(MACM_E_INVALID, "tdm policy is NULL");
+  if (const int rc = tdm_policy_check(p)) return rc;
+  if (!obs || !mask || !health || !actions) return fail(MACM_E_INVALID, "obs/mask/health/actions is NULL");
+  if (reinterpret_cast<uintptr_t>(obs) & 15) return fail(MACM_E_INVALID, "obs must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(actions) & 3) return fail(MACM_E_INVALID, "actions must be 4-byte aligned");
+  if (n_agents < 2) return fail(MACM_E_INVALID, "n_agents must be >= 2");
+  if (rows < 0) return fail(MACM_E_INVALID, "rows must be >= 0");
+  if (rows % n_agents != 0)
+    return fail(MACM_E_INVALID, "rows must be a multiple of n_agents (rows = E * N: row r is agent r % n_agents)");
+  const TdmPolicyArgs M{p->params, noise, logits, p->hidden, 0u};
+  HIP_TRY(launch_policy_tdm(M, obs, mask, health, obs_f64 != 0, n_agents, rows, agents, nullptr, 0.0, actions,
+                            (hipStream_t)stream));
+  return MACM_OK;
+}
+
+int macm_tdm_set_policy(macm_tdm* w, const macm_tdm_policy* p, uint32_t team_mask) {
+  if (!w) return fail(MACM_E_INVALID, "tdm is NULL");
+  if (!p) {
+    w->policy = macm_tdm_policy{0, {0, 0, 0}, nullptr};
+    w->policy_teams = 0;
+    w->policy_all = false;
+    return MACM_OK;
+  }
+  if (const int rc = tdm_policy_check(p)) return rc;
+  if (team_mask == 0) return fail(MACM_E_INVALID, "tdm policy: team_mask is 0 (no team would take the policy)");
+  if (team_mask >> w->cfg.n_teams)
+    return fail(MACM_E_INVALID, "tdm policy: team_mask names a team at or above n_teams = " + std::to_string(w->cfg.n_teams));
+  DeviceGuard g(w->device);
+  const int N = w->P.n_agents;
+  std::vector<uint8_t> ag(N);
+  bool all = true;
+  for (int i = 0; i < N; ++i) {
+    ag[i] = (team_mask >> w->team[i]) & 1u;
+    all = all && ag[i];
+  }
+  if (!w->policy_agents)
+    if (const int rc = dalloc(w->allocs, &w->policy_agents, (size_t)N)) return rc;
+  HIP_TRY(hipDeviceSynchronize());  // a launch in flight may still read the mask of the registration before
+  HIP_TRY(hipMemcpy(w->policy_agents, ag.data(), (size_t)N, hipMemcpyHostToDevice));
+  w->policy = *p;
+  w->policy_teams = team_mask;
+  w->policy_all = all;
+  return MACM_OK;
+}
+
 // As world_autoreset_step: the step's done flags (a private copy) mask the draw and init launches.
 // TB / obs: the step's outputs; the init writes the new initial obs and mask there and leaves the
 // terminal health, alive and winner outputs as the step wrote them.
@@ -629,14 +693,17 @@ static int tdm_rollout_split(macm_tdm* w, const TdmBuffers& TB, const TdmIO& io,
   return MACM_OK;
 }
 
-// macm_tdm_rollout / _traj (bots = false) and macm_tdm_rollout_bots / _traj (bots = true)
+// macm_tdm_rollout / _traj (bots = false), macm_tdm_rollout_bots / _traj (bots = true) and
+// macm_tdm_rollout_policy / _traj (bots = true, pol: the registered policy's params and teams and this
+// call's noise and logits; the other teams' agents keep the bot)
 static int tdm_rollout(macm_tdm* w, const void* actions, int n_steps, const macm_tdm_outputs* out, void* stream,
-                       bool bots, bool traj) {
+                       bool bots, bool traj, const TdmPolicyArgs* pol = nullptr) {
   if (n_steps < 0) return fail(MACM_E_INVALID, "n_steps must be >= 0");
   if (n_steps == 0) return MACM_OK;
   if (!w || !actions) return fail(MACM_E_INVALID, "tdm/actions is NULL");
   if ((bots || traj) && !out) return fail(MACM_E_INVALID, "out is NULL");
   if (bots && (!out->obs || !out->mask)) return fail(MACM_E_INVALID, "out->obs/mask is NULL (the bots act on them)");
+  if (pol && !out->health) return fail(MACM_E_INVALID, "out->health is NULL (the policy reads it)");
   if (w->autoreset && !w->mt_valid) return fail(MACM_E_INVALID, kNoTdmStreams);
   if (const int rc = final_outputs_need(w->autoreset, w->fin, out ? out->obs : nullptr, nullptr,
                                         out ? out->mask : nullptr))
@@ -658,7 +725,8 @@ static int tdm_rollout(macm_tdm* w, const void* actions, int n_steps, const macm
   }
   const TdmBuffers TB = tdm_with_outputs(w, out);
   const unsigned long long astride = bots ? 0ull : (unsigned long long)w->P.n_envs * w->P.n_agents * 4;
-  const TdmIO io = tdm_io(w, actions, out);
+  TdmIO io = tdm_io(w, actions, out);
+  io.policy = pol;
   const RollShape sh(n_steps, astride, traj);
   if (!w->wave) {
     // workgroup step (N > 64): one launch per step (and the bots kernel's), in order; trajectory
@@ -689,9 +757,18 @@ static int tdm_rollout(macm_tdm* w, const void* actions, int n_steps, const macm
         const int rc = tdm_autoreset_step(w, TBk, obs_k, s);
         if (rc) return rc;
       }
-      if (bots)
-        HIP_TRY(launch_bots_combat(obs_k, TBk.mask_out, w->cfg.obs_f64 != 0, (int)N, (long long)EN,
-                                   const_cast<unsigned char*>(act_k) + (traj ? EN * 4 : 0), s));
+      unsigned char* const next = const_cast<unsigned char*>(act_k) + (traj ? EN * 4 : 0);
+      if (bots && !(pol && w->policy_all))
+        HIP_TRY(launch_bots_combat(obs_k, TBk.mask_out, w->cfg.obs_f64 != 0, (int)N, (long long)EN, next, s));
+      if (pol) {  // over the bot's actions: the rows of the policy's teams, noise row k, the logits into the step's row
+        TdmPolicyArgs M = *pol;
+        if (M.noise) M.noise += (size_t)k * EN * kTdmPolicyLogits;
+        if (M.logits) M.logits += kr * EN * kTdmPolicyLogits;
+        // (autoreset: rmask holds this step's done flags; a reset env's health output keeps the terminal health)
+        HIP_TRY(launch_policy_tdm(M, obs_k, TBk.mask_out, TBk.health_out, w->cfg.obs_f64 != 0, (int)N, (long long)EN,
+                                  w->policy_all ? nullptr : w->policy_agents, w->autoreset ? w->rmask : nullptr,
+                                  w->TP.init_health, next, s));
+      }
     }
     return MACM_OK;
   }
@@ -724,6 +801,26 @@ int macm_tdm_rollout_bots(macm_tdm* w, uint8_t* actions, int n_steps, const macm
 int macm_tdm_rollout_bots_traj(macm_tdm* w, uint8_t* actions, int n_steps, const macm_tdm_outputs* traj,
                                void* stream) {
   return tdm_rollout(w, actions, n_steps, traj, stream, true, true);
+}
+
+static int tdm_rollout_policy(macm_tdm* w, uint8_t* actions, int n_steps, const float* noise, float* logits,
+                              const macm_tdm_outputs* out, void* stream, bool traj) {
+  if (n_steps < 0) return fail(MACM_E_INVALID, "n_steps must be >= 0");
+  if (n_steps == 0) return MACM_OK;
+  if (!w) return fail(MACM_E_INVALID, "tdm is NULL");
+  if (!w->policy.params) return fail(MACM_E_INVALID, "no policy is registered (macm_tdm_set_policy)");
+  const TdmPolicyArgs M{w->policy.params, noise, logits, w->policy.hidden, w->policy_teams};
+  return tdm_rollout(w, actions, n_steps, out, stream, true, traj, &M);
+}
+
+int macm_tdm_rollout_policy(macm_tdm* w, uint8_t* actions, int32_t n_steps, const float* noise, float* logits,
+                            const macm_tdm_outputs* out, void* stream) {
+  return tdm_rollout_policy(w, actions, n_steps, noise, logits, out, stream, false);
+}
+
+int macm_tdm_rollout_policy_traj(macm_tdm* w, uint8_t* actions, int32_t n_steps, const float* noise, float* logits,
+                                 const macm_tdm_outputs* traj, void* stream) {
+  return tdm_rollout_policy(w, actions, n_steps, noise, logits, traj, stream, true);
 }
 
 int macm_tdm_observe(macm_tdm* w, const macm_tdm_outputs* out, void* stream) {

@@ -2789,6 +2789,15 @@ template <typename OT>
 struct ObsPolS {};
 template <typename OT>
 struct ObsPolVS {};
+// The closed loop of a TDM world under a registered set policy (macm_tdm_rollout_policy): ObsTdmPol<float> /
+// ObsTdmPol<double>, the same kernel templates with the net of tdm_policy.hpp where the bot is, for the
+// lanes of the policy's teams; ObsTdmPolEv: that of a world with events registered as well. Their argument
+// grows by the policy's fields (after the event pointer). New tags: the bot and plain kernels keep their
+// names and their code.
+template <typename OT>
+struct ObsTdmPol {};
+template <typename OT>
+struct ObsTdmPolEv {};
 template <typename OTA>
 struct ObsTag {
   using type = OTA;
@@ -2796,6 +2805,7 @@ struct ObsTag {
   static constexpr bool pol = false;
   static constexpr bool val = false;
   static constexpr bool smp = false;
+  static constexpr bool tpol = false;
 };
 template <typename OT>
 struct ObsTag<ObsEv<OT>> {
@@ -2804,6 +2814,7 @@ struct ObsTag<ObsEv<OT>> {
   static constexpr bool pol = false;
   static constexpr bool val = false;
   static constexpr bool smp = false;
+  static constexpr bool tpol = false;
 };
 template <typename OT>
 struct ObsTag<ObsPol<OT>> {
@@ -2812,6 +2823,7 @@ struct ObsTag<ObsPol<OT>> {
   static constexpr bool pol = true;
   static constexpr bool val = false;
   static constexpr bool smp = false;
+  static constexpr bool tpol = false;
 };
 template <typename OT>
 struct ObsTag<ObsPolV<OT>> {
@@ -2820,6 +2832,7 @@ struct ObsTag<ObsPolV<OT>> {
   static constexpr bool pol = true;
   static constexpr bool val = true;
   static constexpr bool smp = false;
+  static constexpr bool tpol = false;
 };
 template <typename OT>
 struct ObsTag<ObsPolS<OT>> : ObsTag<ObsPol<OT>> {
@@ -2828,6 +2841,14 @@ struct ObsTag<ObsPolS<OT>> : ObsTag<ObsPol<OT>> {
 template <typename OT>
 struct ObsTag<ObsPolVS<OT>> : ObsTag<ObsPolV<OT>> {
   static constexpr bool smp = true;
+};
+template <typename OT>
+struct ObsTag<ObsTdmPol<OT>> : ObsTag<OT> {
+  static constexpr bool tpol = true;
+};
+template <typename OT>
+struct ObsTag<ObsTdmPolEv<OT>> : ObsTag<ObsEv<OT>> {
+  static constexpr bool tpol = true;
 };
 template <typename OT>
 struct RolloutArgs<ObsEv<OT>> : RolloutArgs<OT> {
@@ -2851,6 +2872,33 @@ template <typename OT>
 struct RolloutArgs<ObsPolVS<OT>> : RolloutArgs<ObsPolV<OT>> {
   SampleArgs smp;
 };
+template <typename OT>
+struct RolloutArgs<ObsTdmPol<OT>> : RolloutArgs<OT> {
+  // noise [K, E, N, 11]: row k decides after step k; logits [E, N, 11], or [K, E, N, 11] with traj
+  TdmPolicyArgs tpol;  // (last: the fields before it keep their offsets)
+};
+template <typename OT>
+struct RolloutArgs<ObsTdmPolEv<OT>> : RolloutArgs<ObsEv<OT>> {
+  TdmPolicyArgs tpol;
+};
+// One lane's decision after step k of a TDM policy rollout: the lanes of the policy's teams take the set
+// policy on row `row` of the step's obs and mask (noise row k, the logits into the step's output row kr),
+// the other lanes bots.combat. reset: the env was reset after the step, whose health output keeps the
+// terminal health; the policy then reads init_health, what macm_tdm_reset_envs writes.
+template <typename OT>
+__device__ __forceinline__ void tdm_policy_act_row(const TdmPolicyArgs& M, const TdmParams& TP, const TdmBuffers& TB, int N,
+                                                   const OT* __restrict__ obs, int lane, size_t row, size_t k, size_t kr,
+                                                   size_t EN, bool reset, uint8_t* __restrict__ pol_out) {
+  const OT* const o = obs + row * (N - 1) * 4;
+  const uint8_t* const m = TB.mask_out + row * (N - 1);
+  if ((M.team_mask >> tdm_team_nb(TP, lane)) & 1u) {
+    const double h = reset ? TP.init_health : TB.health_out[row];
+    tdm_policy_row<OT, true>(M, o, m, N, (float)h, M.noise ? M.noise + (k * EN + row) * kTdmPolicyLogits : nullptr,
+                       pol_out + row * 4, M.logits ? M.logits + (kr * EN + row) * kTdmPolicyLogits : nullptr);
+  } else {
+    bot_combat_row(o, m, N, pol_out + row * 4);
+  }
+}
 // One lane's critic stores of step k of a policy rollout: v is the bootstrap value of the step's output
 // row kr (with_boot) and the value of the obs row the next action is taken from
 __device__ __forceinline__ void value_store_row(const ValueArgs& V, float v, size_t row, size_t k, size_t kr, size_t EN,
@@ -2966,8 +3014,14 @@ static void roll_variant(int& cur, bool closed, const FlockRollExtras& x, int32_
         R.smp = *x.sample;
       });
     if (x.policy) return go(TypeTag<ObsPol<OT>>{}, std::false_type{}, [&](auto& R) { R.pol = *x.policy; });
-  } else if (hit_out) {
-    return go(TypeTag<ObsEv<OT>>{}, std::false_type{}, [&](auto& R) { R.hit_out = hit_out; });
+  } else {
+    if (x.tdm_policy && hit_out)
+      return go(TypeTag<ObsTdmPolEv<OT>>{}, std::false_type{}, [&](auto& R) {
+        R.hit_out = hit_out;
+        R.tpol = *x.tdm_policy;
+      });
+    if (x.tdm_policy) return go(TypeTag<ObsTdmPol<OT>>{}, std::false_type{}, [&](auto& R) { R.tpol = *x.tdm_policy; });
+    if (hit_out) return go(TypeTag<ObsEv<OT>>{}, std::false_type{}, [&](auto& R) { R.hit_out = hit_out; });
   }
   go(TypeTag<OT>{}, std::false_type{}, none);
 }
@@ -3020,8 +3074,10 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
   constexpr bool POL = ObsTag<OTA>::pol;
   constexpr bool VAL = ObsTag<OTA>::val;
   constexpr bool SMP = ObsTag<OTA>::smp;
+  constexpr bool TPOL = ObsTag<OTA>::tpol;
   static_assert(!EV || MODE == kTdm, "combat events are TDM's");
   static_assert(!POL || (MODE == kFlock && !CARRY), "the MLP policy acts in Flock's closed loop");
+  static_assert(!TPOL || (MODE == kTdm && !CARRY), "the set policy acts in TDM's closed loop");
   const int nsteps = A0.nsteps;
   const bool bal = A0.B.sched && nsteps >= kRollBalanceMinSteps;  // as in launch_roll
   // TDM tail observation: blocks beyond the envs only observe (TailObs)
@@ -3114,6 +3170,8 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
             policy_sample_row<OT>(A.pol, A.smp, (int)od, obs, row, (size_t)k, kr, EN, pol_out);
           else if constexpr (POL)
             policy_act_row<OT>(A.pol, (int)od, obs, row, (size_t)k, kr, EN, pol_out);
+          else if constexpr (TPOL)
+            tdm_policy_act_row<OT>(A.tpol, A.TP, TB, N, obs, lane, row, (size_t)k, kr, EN, false, pol_out);
           else if constexpr (MODE == kTdm)
             bot_combat_row(obs + row * (N - 1) * 4, TB.mask_out + row * (N - 1), N, pol_out + row * 4);
           else
@@ -3218,8 +3276,10 @@ hipError_t launch_tdm_rollout_w64(const StepParams& P, const WorldBuffers& B, co
                                   const TailLaunch& tail, hipStream_t s) {
   with_instance<kTdm>(P, io.obs_f64, [&](auto ncap, auto ot, auto scal) {
     using OT = decltype(ot);
+    FlockRollExtras x;
+    x.tdm_policy = io.policy;
     launch_roll<kTdm, decltype(ncap)::value, OT, decltype(scal)::value>(
-        roll_args<OT>(P, B, TP, TB, cur, io, sh, tail), tail.tag ? tail.workers : 0, FlockRollExtras{}, io.hit_out, s);
+        roll_args<OT>(P, B, TP, TB, cur, io, sh, tail), tail.tag ? tail.workers : 0, x, io.hit_out, s);
   });
   return hipGetLastError();
 }

@@ -4,10 +4,11 @@
 // header, so a definition that drifts from its declaration is an ambiguous call, not a new overload.
 // The bundles are host structs: never a kernel parameter (the kernels' argument structs are
 // flock_common.hpp's and flock_step_w64.hip's). The launchers of the learned-policy kernels are declared
-// in policy_mlp.hpp and ppo_row.hpp.
+// in policy_mlp.hpp, tdm_policy.hpp and ppo_row.hpp.
 #pragma once
 #include "flock_common.hpp"
 #include "policy_mlp.hpp"
+#include "tdm_policy.hpp"
 
 namespace macm {
 
@@ -28,6 +29,8 @@ struct FlockIO : StepIO {
 // ... and a TDM launch's (its other outputs: TdmBuffers' *_out)
 struct TdmIO : StepIO {
   int32_t* hit_out = nullptr;  // non-NULL: the kernels that record the combat events (macm_tdm_set_events)
+  // closed-loop rollouts: the set policy of the policy's teams where the bot is (NULL: the bot everywhere)
+  const TdmPolicyArgs* policy = nullptr;
 };
 
 // A rollout launch: nsteps steps, step k's actions at actions + k * astride bytes (0: the closed loop,
@@ -63,6 +66,7 @@ struct FlockRollExtras {
   const PolicyArgs* policy = nullptr;
   const ValueArgs* critic = nullptr;
   const SampleArgs* sample = nullptr;
+  const TdmPolicyArgs* tdm_policy = nullptr;  // TDM rollouts: TdmIO::policy
 };
 
 // launch_final_copy's sources: the step's output rows ([E, ...]) and their sizes per env

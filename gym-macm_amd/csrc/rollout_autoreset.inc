@@ -216,6 +216,15 @@ template <typename OT>
 struct RolloutArArgs<ObsPolVS<OT>> : RolloutArArgs<ObsPolV<OT>> {
   SampleArgs smp;
 };
+// a TDM world under a registered set policy (ObsTdmPol / ObsTdmPolEv): the policy's fields follow
+template <typename OT>
+struct RolloutArArgs<ObsTdmPol<OT>> : RolloutArArgs<OT> {
+  TdmPolicyArgs tpol;  // noise [K, E, N, 11], logits [E, N, 11] or [K, E, N, 11] with A.traj
+};
+template <typename OT>
+struct RolloutArArgs<ObsTdmPolEv<OT>> : RolloutArArgs<ObsEv<OT>> {
+  TdmPolicyArgs tpol;
+};
 
 // env_rollout_w64 with the in-launch reset; no tail or split observation (their pose snapshots know
 // nothing of a mid-launch respawn: TDM observes inside the step).
@@ -228,8 +237,10 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
   constexpr bool POL = ObsTag<OTA>::pol;
   constexpr bool VAL = ObsTag<OTA>::val;
   constexpr bool SMP = ObsTag<OTA>::smp;
+  constexpr bool TPOL = ObsTag<OTA>::tpol;
   static_assert(!EV || MODE == kTdm, "combat events are TDM's");
   static_assert(!POL || (MODE == kFlock && !CARRY), "the MLP policy acts in Flock's closed loop");
+  static_assert(!TPOL || (MODE == kTdm && !CARRY), "the set policy acts in TDM's closed loop");
   const int nsteps = R0.A.nsteps;
   const bool bal = R0.A.B.sched && nsteps >= kRollBalanceMinSteps;  // as in launch_roll_ar
   const int env = bal ? (int)R0.A.B.sched[R0.A.sched_off + blockIdx.x] : (int)blockIdx.x;
@@ -344,6 +355,8 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(4))) void env
             policy_sample_row<OT>(R.pol, R.smp, (int)od, obs, row, (size_t)k, kr, EN, pol_out);
           else if constexpr (POL)
             policy_act_row<OT>(R.pol, (int)od, obs, row, (size_t)k, kr, EN, pol_out);
+          else if constexpr (TPOL)  // a reset env: init_health (the step's health output keeps the terminal one)
+            tdm_policy_act_row<OT>(R.tpol, A.TP, TB, N, obs, lane, row, (size_t)k, kr, EN, dn != 0, pol_out);
           else if constexpr (MODE == kTdm)
             bot_combat_row(obs + row * (N - 1) * 4, TB.mask_out + row * (N - 1), N, pol_out + row * 4);
           else
@@ -400,8 +413,10 @@ hipError_t launch_tdm_rollout_ar_w64(const StepParams& P, const WorldBuffers& B,
                                      const ResetLaunch& r, hipStream_t s) {
   with_instance<kTdm>(P, io.obs_f64, [&](auto ncap, auto ot, auto scal) {
     using OT = decltype(ot);
+    FlockRollExtras x;
+    x.tdm_policy = io.policy;
     launch_roll_ar<kTdm, decltype(ncap)::value, OT, decltype(scal)::value>(
-        roll_args<OT>(P, B, TP, TB, cur, io, sh, TailLaunch{}), FlockRollExtras{}, r, io.hit_out, s);
+        roll_args<OT>(P, B, TP, TB, cur, io, sh, TailLaunch{}), x, r, io.hit_out, s);
   });
   return hipGetLastError();
 }

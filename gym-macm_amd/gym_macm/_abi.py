@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64,
-                    c_uint8, c_uint64, c_void_p)
+                    c_uint8, c_uint32, c_uint64, c_void_p)
 
 ACTION_DISCRETE, ACTION_CONTINUOUS = 0, 1
 REWARD_BINARY, REWARD_LINEAR = 0, 1
@@ -94,6 +94,12 @@ class MacmValueMlp(Structure):
     W1[in][hidden], b1, (W2[hidden][hidden], b2), W3[hidden][1], b3, 16-byte aligned."""
     _fields_ = [("in_dim", c_int32), ("hidden", c_int32), ("n_hidden", c_int32), ("reserved", c_int32),
                 ("params", c_void_p)]
+
+
+class MacmTdmPolicy(Structure):
+    """macm_tdm_policy: a float32 set policy over TDM obs slots; params is a device pointer to
+    W1[4][hidden], b1, W2[hidden + 1][hidden], b2, W3[hidden][11], b3, 16-byte aligned; reserved is 0."""
+    _fields_ = [("hidden", c_int32), ("reserved", c_int32 * 3), ("params", c_void_p)]
 
 
 class MacmSampleConfig(Structure):
@@ -332,6 +338,13 @@ SIGNATURES = {
                                 POINTER(MacmValueMlp), c_void_p, c_int32, c_int64] + [c_void_p] * 5 +
                         [c_int32, POINTER(c_void_p), POINTER(c_int64), c_int32, c_double, c_void_p, c_int64, c_void_p,
                          c_void_p, c_int64, c_void_p]),
+    "macm_policy_tdm": (c_int, [POINTER(MacmTdmPolicy), c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "macm_tdm_set_policy": (c_int, [c_void_p, POINTER(MacmTdmPolicy), c_uint32]),
+    "macm_tdm_rollout_policy": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, POINTER(MacmTdmOutputs),
+                                        c_void_p]),
+    "macm_tdm_rollout_policy_traj": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                             POINTER(MacmTdmOutputs), c_void_p]),
     "macm_bots_flock": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
     "macm_bots_combat": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
 }

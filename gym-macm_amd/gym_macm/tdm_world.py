@@ -83,6 +83,7 @@ class TdmWorld:
         self.team = np.array(team, np.int32)
         self.final_obs = self.final_mask = self.final_length = self.final_ends = None  # set_final_outputs
         self.hit_id = None  # set_events
+        self.policy = self.policy_teams = None  # set_policy
         if autoreset:
             self.set_autoreset(True)
         if final_obs:
@@ -317,6 +318,72 @@ class TdmWorld:
         _abi.check(self.L.macm_tdm_rollout_bots(self.h, _ptr(actions), int(n_steps), ctypes.byref(self._out),
                                                 self._stream()), "macm_tdm_rollout_bots")
         return self.outputs()
+
+    def policy_agents(self, teams=None) -> torch.Tensor:
+        """uint8 [N] on the device: 1 for the agents of ``teams`` (None: every team), the ``agents`` argument
+        of TdmSetPolicy.act."""
+        sel = range(int(self.cfg.n_teams)) if teams is None else [int(t) for t in teams]
+        return torch.from_numpy(np.isin(self.team, sel).astype(np.uint8)).to(self.device)
+
+    def set_policy(self, pol, teams=None) -> None:
+        """Register the actor of rollout_policy (macm_tdm_set_policy): a gym_macm.tdm_policy.TdmSetPolicy
+        for the agents of ``teams`` (team indices; None = every team); the other teams' agents keep
+        bots.combat. The library keeps a pointer into ``pol.params`` and reads it at every launch, so new
+        values written in place take effect without a second call; this object keeps ``pol`` alive.
+        None clears the registration."""
+        if pol is None:
+            _abi.check(self.L.macm_tdm_set_policy(self.h, None, 0), "macm_tdm_set_policy")
+            self.policy = self.policy_teams = None
+            return
+        if pol.device != self.device:
+            raise ValueError("the policy's params must live on the world's device")
+        sel = list(range(int(self.cfg.n_teams))) if teams is None else [int(t) for t in teams]
+        if any(t < 0 or t >= 32 for t in sel):
+            raise ValueError("teams must be team indices")
+        tm = 0
+        for t in sel:
+            tm |= 1 << t
+        _abi.check(self.L.macm_tdm_set_policy(self.h, ctypes.byref(pol.struct()), tm), "macm_tdm_set_policy")
+        self.policy, self.policy_teams = pol, tuple(sorted(set(sel)))
+
+    def _check_policy_io(self, K, noise, logits, traj):
+        from .tdm_policy import N_LOGITS
+        E, N = self.E, self.N
+        want_l = (K, E, N, N_LOGITS) if traj else (E, N, N_LOGITS)
+        for name, t, shp in (("noise", noise, (K, E, N, N_LOGITS)), ("logits", logits, want_l)):
+            if t is not None and (t.device != self.device or not t.is_contiguous() or t.dtype != torch.float32
+                                  or tuple(t.shape) != shp):
+                raise ValueError(f"{name} must be a contiguous float32 {list(shp)} tensor on the world's device")
+        return _ptr(noise), _ptr(logits)
+
+    def rollout_policy(self, actions: torch.Tensor, n_steps: int, noise: torch.Tensor = None,
+                       logits: torch.Tensor = None):
+        """n_steps of the closed loop step -> actor -> step in one launch (macm_tdm_rollout_policy): the
+        registered policy for its teams, bots.combat for the others. actions uint8 [E, N, 4]: the first
+        step's on entry, the actors' next on return; noise float32 [n_steps, E, N, 11] or None (the argmax);
+        logits float32 [E, N, 11] or None: the last step's, the rows of bot-driven agents not written."""
+        K = int(n_steps)
+        if (actions.device != self.device or not actions.is_contiguous() or actions.dtype != torch.uint8
+                or tuple(actions.shape) != (self.E, self.N, 4)):
+            raise ValueError(f"actions must be a contiguous uint8 [{self.E},{self.N},4] tensor on the world's device")
+        pn, pl = self._check_policy_io(K, noise, logits, False)
+        _abi.check(self.L.macm_tdm_rollout_policy(self.h, _ptr(actions), K, pn, pl, ctypes.byref(self._out),
+                                                  self._stream()), "macm_tdm_rollout_policy")
+        return self.outputs()
+
+    def rollout_policy_traj(self, actions: torch.Tensor, n_steps: int, traj: dict = None, noise: torch.Tensor = None,
+                            logits: torch.Tensor = None) -> dict:
+        """As rollout_policy(), keeping every step's outputs and actions (macm_tdm_rollout_policy_traj):
+        actions uint8 [n_steps + 1, E, N, 4], row 0 the first step's; step k's decisions in row k + 1, taken
+        from obs row k with noise row k, their logits in row k of logits [n_steps, E, N, 11]."""
+        K = int(n_steps)
+        if (actions.device != self.device or not actions.is_contiguous() or actions.dtype != torch.uint8
+                or tuple(actions.shape) != (K + 1, self.E, self.N, 4)):
+            raise ValueError(f"actions must be a contiguous uint8 [{K + 1},{self.E},{self.N},4] tensor on the "
+                             "world's device")
+        pn, pl = self._check_policy_io(K, noise, logits, True)
+        fn = lambda h, a, k, out, s: self.L.macm_tdm_rollout_policy_traj(h, a, k, pn, pl, out, s)
+        return self._traj_call(fn, "macm_tdm_rollout_policy_traj", actions, K, traj)
 
     def rollout_bots_raw(self, actions_ptr: int, n_steps: int, stream_handle: int) -> None:
         self.L.macm_tdm_rollout_bots(self.h, ctypes.c_void_p(actions_ptr), int(n_steps), ctypes.byref(self._out),

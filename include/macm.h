@@ -489,7 +489,8 @@ int macm_world_rollout_bots_traj(macm_world* w, uint8_t* actions, int32_t n_step
  *           W3[hidden][9], b3[9].
  * hidden is 16 or 32, n_hidden 1 or 2, in_dim 4 (polar) or 6 (cartesian), reserved 0.
  * Flock worlds with discrete actions only: a TDM observation is a masked set, not a fixed vector, and
- * continuous actions have no heads (both out of scope). Additive: MACM_ABI_VERSION stays 9.
+ * has a policy of its own (macm_tdm_policy, below); continuous actions have no heads (out of scope).
+ * Additive: MACM_ABI_VERSION stays 9.
  */
 typedef struct macm_policy_mlp {
   int32_t in_dim, hidden, n_hidden, reserved;
@@ -1110,6 +1111,80 @@ int macm_tdm_rollout_traj(macm_tdm* w, const void* actions, int32_t n_steps, con
                           void* stream);
 int macm_tdm_rollout_bots_traj(macm_tdm* w, uint8_t* actions, int32_t n_steps, const macm_tdm_outputs* traj,
                                void* stream);
+
+/*
+ * A learned policy as the actor of TDM's closed loop: a permutation-invariant float32 net over the
+ * [N-1, 4] observation slots of an agent, in the place of the scripted bot, with a team mask so that
+ * one side learns against bots.combat on the other. Defined so that it can be checked bit for bit; all
+ * arithmetic float32, the conventions of macm_policy_mlp (explicit fmaf chains with k ascending and one
+ * rounding per step; relu(v) = v > 0 ? v : +0.0f). For agent i of an env with N agents, with its obs row
+ * o[N-1][4] as stored (float64 obs round to nearest), its mask row m[N-1] and its health h (the double
+ * of macm_tdm_outputs.health rounded to float32):
+ *   encoder for every slot k with m[k] != 0: e_k[j] = relu(b1[j] + sum_q W1[q][j] o[k][q]), q = 0..3 ascending;
+ *   pool    g[j] = +0.0f, then g[j] = e_k[j] > g[j] ? e_k[j] : g[j] over the live slots. After the relu no e
+ *           is NaN or negative, so the pooled value does not depend on the order of the slots; a row with
+ *           no live slot (a dead agent, the last one standing) pools to zeros and still yields an action;
+ *           what a masked slot holds (NaN, inf, -0) changes nothing;
+ *   trunk   u = (g[0..H-1], h); t[j] = relu(b2[j] + sum_k W2[k][j] u[k]), k = 0..H ascending (the health
+ *           is input k = H);
+ *   head    z[c] = b3[c] + sum_k W3[k][c] t[k]: 11 logits of MultiDiscrete([3, 3, 3, 2]), heads 0..2 at
+ *           z[3h + c], head 3 (attack) at z[9] and z[10];
+ *   action  the rule of macm_policy_mlp, word for word, per head: z[c] + noise[c] if noise is given (one
+ *           float32 add), then the lowest c with the largest value by `>` from -inf. 4 bytes: forward,
+ *           lateral, rotation, attack.
+ *   params: device float32, 16-byte aligned, row-major [in][out]:
+ *           W1[4][H], b1[H], W2[H+1][H], b2[H], W3[H][11], b3[11] (1,611 floats at H = 32).
+ * hidden (H) is 16 or 32, reserved 0. The caller supplies the noise. Out of scope: a critic, gradients on
+ * the device, an in-launch draw, continuous actions. Additive: MACM_ABI_VERSION stays 9.
+ */
+typedef struct macm_tdm_policy {
+  int32_t hidden;
+  int32_t reserved[3];
+  const float* params;
+} macm_tdm_policy;
+
+/*
+ * The policy's decision for `rows` agent rows (rows = E * n_agents: obs [rows, N-1, 4] float32 or float64
+ * as obs_f64 and 16-byte aligned, mask [rows, N-1], health [rows] float64), as macm_bots_combat is for the
+ * bot. agents: uint8 [n_agents] on the device, or NULL (every agent); where agents[row % n_agents] == 0
+ * the row's action bytes and logits row are left untouched, so a caller can run the bot first and the
+ * policy over it. noise [rows, 11] or NULL; actions uint8 [rows, 4] (4-byte aligned); logits [rows, 11] or
+ * NULL. MACM_E_INVALID, nothing launched: p NULL, hidden outside 16 / 32, reserved != 0, params NULL or
+ * misaligned, obs / mask / health / actions NULL or misaligned, n_agents < 2, rows < 0 or no multiple of
+ * n_agents.
+ */
+int macm_policy_tdm(const macm_tdm_policy* p, const void* obs, const uint8_t* mask, const double* health,
+                    int32_t obs_f64, int32_t n_agents, int64_t rows, const uint8_t* agents, const float* noise,
+                    uint8_t* actions, float* logits, void* stream);
+
+/*
+ * Registers the policy of macm_tdm_rollout_policy, as macm_world_set_policy: the world keeps the struct,
+ * not the params buffer; a later launch reads params the learner overwrote in place. p NULL clears the
+ * registration (team_mask is ignored). Bit t of team_mask gives team t to the policy; the agents of the
+ * other teams keep bots.combat. MACM_E_INVALID, nothing changed: a NULL world, a struct the one-shot
+ * call would refuse, team_mask 0 or with a bit at or above n_teams. Synchronises the device (the team
+ * mask is copied to it).
+ */
+int macm_tdm_set_policy(macm_tdm* w, const macm_tdm_policy* p, uint32_t team_mask);
+
+/*
+ * n_steps of the closed loop `step -> actor -> step`, as macm_tdm_rollout_bots / _bots_traj with the
+ * registered policy as the actor of its teams: one launch on the wave path (N <= 64); on the workgroup
+ * path the launches of macm_tdm_step, the bots kernel and macm_policy_tdm on the caller's stream.
+ *   actions: [E, N, 4] in and out; trajectory form [n_steps + 1, E, N, 4], row 0 given, step k writes row k + 1.
+ *   noise:   [n_steps, E, N, 11] or NULL; row k is used for the decision taken after step k.
+ *   logits:  [E, N, 11] (the last step's remain), trajectory form [n_steps, E, N, 11], or NULL; the rows of
+ *            bot-driven agents are not written.
+ * out->obs, out->mask and out->health must be set. With autoreset on, the agents of a reset env decide on
+ * its new initial obs and mask and on init_health (the step's health output keeps the terminal health),
+ * as the per-step loop (macm_tdm_step, macm_tdm_reset_envs(done), macm_bots_combat, macm_policy_tdm) sees
+ * them. Events and final outputs as in every other form. MACM_E_INVALID without a registered policy.
+ * n_steps = 0 does nothing. Same results as n_steps of the per-step loop, bit for bit.
+ */
+int macm_tdm_rollout_policy(macm_tdm* w, uint8_t* actions, int32_t n_steps, const float* noise, float* logits,
+                            const macm_tdm_outputs* out, void* stream);
+int macm_tdm_rollout_policy_traj(macm_tdm* w, uint8_t* actions, int32_t n_steps, const float* noise, float* logits,
+                                 const macm_tdm_outputs* traj, void* stream);
 
 /* TDM.get_obs of the current state without stepping. */
 int macm_tdm_observe(macm_tdm* w, const macm_tdm_outputs* out, void* stream);
