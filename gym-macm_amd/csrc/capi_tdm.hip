@@ -414,6 +414,43 @@ int macm_policy_tdm(const macm_tdm_policy* p, const void* obs, const uint8_t* ma
   return MACM_OK;
 }
 
+// The workspace of macm_tdm_policy_grad: one partial of the larger net per wave
+static int64_t tdm_grad_workspace_bytes(int64_t rows) {
+  return (int64_t)mlp_grad_partials(rows) * tdm_policy_n_params(32) * (int64_t)sizeof(float);
+}
+
+int macm_tdm_grad_workspace(int64_t rows, int64_t* bytes) {
+  if (!bytes) return fail(MACM_E_INVALID, "tdm grad: bytes is NULL");
+  if (rows < 0) return fail(MACM_E_INVALID, "tdm grad: rows must be >= 0");
+  *bytes = tdm_grad_workspace_bytes(rows);
+  return MACM_OK;
+}
+
+int macm_tdm_policy_grad(const macm_tdm_policy* p, const void* obs, const uint8_t* mask, const double* health,
+                         int32_t obs_f64, int32_t n_agents, int64_t rows, const uint8_t* agents, const float* dlogits,
+                         float* grad, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!p) return fail(MACM_E_INVALID, "tdm policy is NULL");
+  if (const int rc = tdm_policy_check(p)) return rc;
+  if (!obs || !mask || !health) return fail(MACM_E_INVALID, "tdm grad: obs/mask/health is NULL");
+  if (!dlogits || !grad) return fail(MACM_E_INVALID, "tdm grad: dlogits/grad is NULL");
+  if (reinterpret_cast<uintptr_t>(obs) & 15) return fail(MACM_E_INVALID, "tdm grad: obs must be 16-byte aligned");
+  if (n_agents < 2) return fail(MACM_E_INVALID, "tdm grad: n_agents must be >= 2");
+  if (rows < 0) return fail(MACM_E_INVALID, "tdm grad: rows must be >= 0");
+  if (rows % n_agents != 0)
+    return fail(MACM_E_INVALID,
+                "tdm grad: rows must be a multiple of n_agents (rows = E * N: row r is agent r % n_agents)");
+  if (rows > 0 && !workspace) return fail(MACM_E_INVALID, "tdm grad: workspace is NULL");
+  if (rows > 0 && (reinterpret_cast<uintptr_t>(workspace) & 15))
+    return fail(MACM_E_INVALID, "tdm grad: workspace must be 16-byte aligned");
+  if (rows > 0 && workspace_bytes < tdm_grad_workspace_bytes(rows))
+    return fail(MACM_E_INVALID, "tdm grad: workspace_bytes " + std::to_string(workspace_bytes) + " is below the " +
+                                    std::to_string(tdm_grad_workspace_bytes(rows)) + " of macm_tdm_grad_workspace");
+  const TdmPolicyArgs M{p->params, nullptr, nullptr, p->hidden, 0u};
+  HIP_TRY(launch_tdm_policy_grad(M, obs, mask, health, obs_f64 != 0, n_agents, rows, agents, dlogits, grad,
+                                 (float*)workspace, (hipStream_t)stream));
+  return MACM_OK;
+}
+
 int macm_tdm_set_policy(macm_tdm* w, const macm_tdm_policy* p, uint32_t team_mask) {
   if (!w) return fail(MACM_E_INVALID, "tdm is NULL");
   if (!p) {

@@ -159,4 +159,11 @@ hipError_t launch_policy_tdm(const TdmPolicyArgs& M, const void* obs, const uint
                              bool obs_f64, int N, long long rows, const uint8_t* agents, const uint8_t* reset,
                              double init_health, uint8_t* act, hipStream_t s);
 
+// host side (tdm_policy_grad.hip): dL/dparams of the set policy from dlogits [rows, 11] (macm_tdm_policy_grad);
+// M.noise, M.logits and M.team_mask are not read. One wave writes one partial [tdm_policy_n_params(hidden)]
+// into the workspace, mlp_grad_partials(rows) of them (policy_mlp.hpp); rows <= 0 writes zeros.
+hipError_t launch_tdm_policy_grad(const TdmPolicyArgs& M, const void* obs, const uint8_t* mask, const double* health,
+                                  bool obs_f64, int N, long long rows, const uint8_t* agents, const float* dlogits,
+                                  float* grad, float* workspace, hipStream_t s);
+
 }  // namespace macm

@@ -340,6 +340,9 @@ SIGNATURES = {
                          c_void_p, c_int64, c_void_p]),
     "macm_policy_tdm": (c_int, [POINTER(MacmTdmPolicy), c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "macm_tdm_grad_workspace": (c_int, [c_int64, POINTER(c_int64)]),
+    "macm_tdm_policy_grad": (c_int, [POINTER(MacmTdmPolicy), c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "macm_tdm_set_policy": (c_int, [c_void_p, POINTER(MacmTdmPolicy), c_uint32]),
     "macm_tdm_rollout_policy": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, POINTER(MacmTdmOutputs),
                                         c_void_p]),

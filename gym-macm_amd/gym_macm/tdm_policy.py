@@ -20,8 +20,13 @@ The definition is include/macm.h's (macm_tdm_policy), all float32 fmaf chains wi
 
 ``params`` is one flat device tensor, W[in][out] row-major then the bias, layer after layer:
 W1[4][H], b1[H], W2[H + 1][H], b2[H], W3[H][11], b3[11]. The library reads it at every launch, so a
-learner that writes new values into it in place needs no second registration. ``torch_logits`` states
-the same function in differentiable torch, for a learner's update under autograd.
+learner that writes new values into it in place needs no second registration.
+
+A learner's update runs under torch autograd without a copy of the net: with ``pol.params.requires_grad_()``,
+``pol.forward(obs, mask, health)`` returns the logits with the bits the rollout stored, and its backward is
+one launch of the gradient kernel (macm_tdm_policy_grad) into ``params.grad``; it keeps obs, mask and health
+and no per-slot activation. ``torch_logits`` states the same function in plain differentiable torch: the
+portable statement, with no bit claim.
 """
 from __future__ import annotations
 
@@ -158,6 +163,67 @@ class TdmSetPolicy:
                                                   p(noise), p(out), p(logits), _stream(obs)), "macm_policy_tdm")
         return out
 
+    def _check_agents(self, agents, N):
+        if agents is not None and (agents.device != self.device or not agents.is_contiguous()
+                                   or agents.dtype != torch.uint8 or tuple(agents.shape) != (N,)):
+            raise ValueError(f"agents must be a contiguous uint8 [{N}] tensor on the policy's device")
+
+    def _logits(self, obs, mask, health, agents=None):
+        """macm_policy_tdm's logits [..., N, 11] (the actions go to a scratch tensor); zeros in the rows of
+        the agents outside ``agents``."""
+        lead = tuple(health.shape)
+        alloc = torch.zeros if agents is not None else torch.empty
+        logits = alloc(lead + (N_LOGITS,), dtype=torch.float32, device=self.device)
+        scratch = torch.empty(lead + (4,), dtype=torch.uint8, device=self.device)
+        self.act(obs, mask, health, logits=logits, out=scratch, agents=agents)
+        return logits
+
+    def forward(self, obs: torch.Tensor, mask: torch.Tensor, health: torch.Tensor,
+                agents: torch.Tensor = None) -> torch.Tensor:
+        """The logits [..., N, 11] for obs [..., N, N-1, 4], mask [..., N, N-1] and health [..., N] with the
+        bits of macm_policy_tdm and the rollouts; where ``params.requires_grad`` is set (and grad mode is on) the
+        result is differentiable with respect to params: its backward is one launch of the gradient kernel,
+        which recomputes the activations. agents: uint8 [N] on the device or None; the rows of agents whose
+        entry is 0 are zeros and take no part in the gradient."""
+        self._check_inputs(obs, mask, health)
+        self._check_agents(agents, int(health.shape[-1]))
+        if obs.requires_grad or health.requires_grad:
+            raise ValueError("obs and health must not require grad (the policy has no gradient with respect to them)")
+        if self.params.requires_grad and torch.is_grad_enabled():
+            return _TdmForward.apply(self.params, obs, mask, health, agents, self)
+        return self._logits(obs, mask, health, agents)
+
+    def grad_workspace_bytes(self, rows: int) -> int:
+        n = ctypes.c_int64(0)
+        _abi.check(_abi.lib().macm_tdm_grad_workspace(int(rows), ctypes.byref(n)), "macm_tdm_grad_workspace")
+        return int(n.value)
+
+    def param_grad(self, obs: torch.Tensor, mask: torch.Tensor, health: torch.Tensor, dlogits: torch.Tensor,
+                   agents: torch.Tensor = None) -> torch.Tensor:
+        """dL/dparams (float32 [n_params], a new tensor) from dlogits = dL/dlogits (float32 [..., N, 11]) over
+        the rows of ``forward``, on the current stream (macm_tdm_policy_grad). The rows of agents whose entry in
+        ``agents`` is 0 are not read. The workspace is this object's, one per row count: calls on one object
+        belong on one stream."""
+        lead = self._check_inputs(obs, mask, health)
+        N = int(lead[-1])
+        self._check_agents(agents, N)
+        if (dlogits.device != self.device or not dlogits.is_contiguous() or dlogits.dtype != torch.float32
+                or tuple(dlogits.shape) != lead + (N_LOGITS,)):
+            raise ValueError(f"dlogits must be a contiguous float32 {lead + (N_LOGITS,)} tensor on the policy's device")
+        rows = health.numel()
+        cache = self.__dict__.setdefault("_grad_ws", {})
+        ws = cache.get(rows)
+        if ws is None:
+            ws = cache[rows] = torch.empty((max(self.grad_workspace_bytes(rows), 16),), dtype=torch.uint8,
+                                           device=self.device)
+        grad = torch.empty_like(self.params, requires_grad=False)
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            _abi.check(_abi.lib().macm_tdm_policy_grad(
+                ctypes.byref(self._struct), p(obs), p(mask), p(health), 1 if obs.dtype == torch.float64 else 0, N, rows,
+                p(agents), p(dlogits), p(grad), p(ws), ws.numel(), _stream(obs)), "macm_tdm_policy_grad")
+        return grad
+
     def torch_logits(self, obs: torch.Tensor, mask: torch.Tensor, health: torch.Tensor,
                      params: torch.Tensor = None) -> torch.Tensor:
         """The 11 logits [..., N, 11] as plain differentiable torch, in the dtype of ``params`` (default: this
@@ -186,3 +252,23 @@ class TdmSetPolicy:
         u = torch.cat([g, health.to(torch.float32).to(P.dtype).unsqueeze(-1)], dim=-1)
         t = relu(u @ W2 + b2)
         return t @ W3 + b3
+
+
+class _TdmForward(torch.autograd.Function):
+    """pol.forward(obs, mask, health) as a function of pol.params: the one-shot kernel forward, the gradient
+    kernel backward. Only obs, mask and health (and agents) are kept for the backward, and params for
+    autograd's check that they were not overwritten between the two: the backward recomputes the activations
+    from the params as they stand."""
+
+    @staticmethod
+    def forward(ctx, params, obs, mask, health, agents, pol):
+        ctx.pol, ctx.agents = pol, agents
+        ctx.save_for_backward(params, obs, mask, health)
+        return pol._logits(obs, mask, health, agents)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        _, obs, mask, health = ctx.saved_tensors
+        g = ctx.pol.param_grad(obs, mask, health, gout.to(torch.float32).contiguous(), ctx.agents)
+        return g, None, None, None, None, None

@@ -1134,8 +1134,8 @@ int macm_tdm_rollout_bots_traj(macm_tdm* w, uint8_t* actions, int32_t n_steps, c
  *           lateral, rotation, attack.
  *   params: device float32, 16-byte aligned, row-major [in][out]:
  *           W1[4][H], b1[H], W2[H+1][H], b2[H], W3[H][11], b3[11] (1,611 floats at H = 32).
- * hidden (H) is 16 or 32, reserved 0. The caller supplies the noise. Out of scope: a critic, gradients on
- * the device, an in-launch draw, continuous actions. Additive: MACM_ABI_VERSION stays 9.
+ * hidden (H) is 16 or 32, reserved 0. The caller supplies the noise. Out of scope: a critic, an in-launch
+ * draw, continuous actions. Additive: MACM_ABI_VERSION stays 9.
  */
 typedef struct macm_tdm_policy {
   int32_t hidden;
@@ -1156,6 +1156,44 @@ typedef struct macm_tdm_policy {
 int macm_policy_tdm(const macm_tdm_policy* p, const void* obs, const uint8_t* mask, const double* health,
                     int32_t obs_f64, int32_t n_agents, int64_t rows, const uint8_t* agents, const float* noise,
                     uint8_t* actions, float* logits, void* stream);
+
+/*
+ * Parameter gradients of the set policy: from dL/dlogits of every agent row to dL/dparams, as
+ * macm_policy_grad is for the MLP, so that a TDM learner's update keeps no per-slot activation. The
+ * arguments before dlogits are macm_policy_tdm's. All arithmetic is float32.
+ *   The forward pass is macm_tdm_policy's as defined above, bit for bit: o (the slots as the forward read
+ *   them: a float64 obs rounded to float32), e_k, g, u = (g, float32(health)), t. With d3 = dlogits of the
+ *   row, and every relu derivative taken from the forward's own stored activation (0 for 0, -0 and NaN):
+ *     gW3[k][c] = sum over rows r of t[r][k] * d3[r][c]              gb3[c] = sum_r d3[r][c]
+ *     d2[r][j]  = (t[r][j] > 0) ? sum_c W3[j][c] * d3[r][c] : 0
+ *     gW2[k][j] = sum_r u[r][k] * d2[r][j] for k = 0..H (row H is the health row)
+ *     gb2[j]    = sum_r d2[r][j]
+ *     dg[r][j]  = (g[r][j] > 0) ? sum_i W2[j][i] * d2[r][i] : 0      (the health gets no gradient)
+ *   The pool: unit j of row r has a winner k*(r, j), the lowest live slot k with e_k[j] == g[j], and only
+ *   when g[j] > 0: the slot at which the forward's `e > g ? e : g` scan last changed g[j]. A unit with
+ *   g[j] == 0 (the empty set, every live e <= 0, NaN pre-activations) has no winner: it contributes exact
+ *   zeros to layer 1 and no slot is read for it. A masked slot is never a winner and never read into a
+ *   gradient, whatever it holds. Over the (r, j) that have a winner:
+ *     gW1[q][j] = sum_r o[r][k*][q] * dg[r][j]                       gb1[j] = sum_r dg[r][j]
+ *   Where agents[row % n_agents] == 0 the row takes no part: its obs, mask, health and dlogits are not
+ *   read. There is no gradient with respect to obs or health.
+ *   grad has the layout of params and is overwritten, not accumulated; rows = 0 writes zeros. Non-finite
+ *   values in live slots give unspecified results. The association of the sums is the kernel's and a
+ *   function of `rows` alone: no floating-point atomics, partial sums combined in a fixed order, so two
+ *   calls with the same arguments give the same bits on any stream.
+ * The caller owns the workspace (device memory, 16-byte aligned) of at least macm_tdm_grad_workspace(rows)
+ * bytes: a function of rows only, nondecreasing in rows and constant from 2048 * 64 rows on. Its contents
+ * after a call are unspecified; two calls in flight at once need a workspace each. Everything is ordered
+ * on `stream`. Additive: MACM_ABI_VERSION stays 9.
+ * MACM_E_INVALID, with a message and nothing launched (decided before any device call): everything
+ * macm_policy_tdm refuses of p, obs, mask, health, n_agents and rows; dlogits or grad NULL; workspace NULL,
+ * misaligned or workspace_bytes too small while rows > 0; macm_tdm_grad_workspace: rows < 0 or bytes NULL.
+ */
+int macm_tdm_grad_workspace(int64_t rows, int64_t* bytes);
+int macm_tdm_policy_grad(const macm_tdm_policy* p, const void* obs, const uint8_t* mask, const double* health,
+                         int32_t obs_f64, int32_t n_agents, int64_t rows, const uint8_t* agents,
+                         const float* dlogits /* [rows, 11] */, float* grad /* [n_params] */, void* workspace,
+                         int64_t workspace_bytes, void* stream);
 
 /*
  * Registers the policy of macm_tdm_rollout_policy, as macm_world_set_policy: the world keeps the struct,
